@@ -6,8 +6,16 @@ penalty, both Adam steps, bf16 storage with fp32 accumulation.  Synthetic data:
 reals U[-1,1) resident in HBM, latents drawn on the GPU by the pg_randn kernel,
 random-init weights (reference init: W ~ N(0,1), b = 0).
 
-Launch:  python bench.py [--gpus N --steps K --warmup W]
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
          (N > 1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...)
+A plain run sets up, warms up (W steps, at least the three after which the step is replayed),
+times the K steps and prints the line.  --full adds what
+the headline figure does not need: the host enqueue time per step (three more untimed
+steps), the per-kernel roofline (event timers on the last timed step, which then runs
+eagerly, and one isolated untimed step; PG_BENCH_SHAPES / PG_BENCH_LAUNCHES dumps) and the
+CPU baseline; without it those fields of the line are null.  --dump-outputs DIR writes what
+the last timed step returned (img_real, img_fake, the losses) as DIR/<name>.npy; the inputs
+are seeded, so two builds run with the same arguments can be compared array for array.
 The timed step is ProgressiveGAN.train_step (the path train.py runs).  One process per
 GPU; gradients all-reduced (mean) over RCCL in per-layer buckets as the backward
 finishes them (pggan_amd.dp), overlapped with the work that does not depend on them
@@ -54,11 +62,19 @@ def parse():
     p.add_argument("--batch", type=int, default=4)
     p.add_argument("--alpha", type=float, default=1.0)
     p.add_argument("--dtype", choices=["bf16", "f32"], default="bf16")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline figure does not need: the host enqueue "
+                        "time per step, the per-kernel roofline (event timers on the last timed "
+                        "step and one isolated step) and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="after the timed steps, write what the last one returned (train_step's "
+                        "images, the losses) as DIR/<name>.npy")
     p.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="0: the process's CPU share (OMP_NUM_THREADS, else os.cpu_count())")
     p.add_argument("--gp-mode", choices=["r1", "wgan-gp"], default="r1")
-    p.add_argument("--no-kernel-events", action="store_true")
+    p.add_argument("--no-kernel-events", action="store_true",
+                   help="with --full: no per-kernel timers (a plain run has none)")
     p.add_argument("--graph", action="store_true",
                    help="replay the step as a hipGraph from the second step on (one process)")
     p.add_argument("--eager", action="store_true",
@@ -69,7 +85,10 @@ def parse():
                         "group), to measure the bookkeeping's cost against the plain step")
     p.add_argument("--dp-bucket-mb", type=float, default=64.0,
                    help="DP all-reduce bucket size (config dp_bucket_mb)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def conv_bytes(x, wpk, y, kw):
@@ -308,6 +327,26 @@ def cpu_baseline(args, steps=1):
                        f"(fp32, torch CPU, torch.set_num_threads({threads})): {dt:.1f} s")
 
 
+# --dump-outputs: an array of more elements than this is written as a sample of this many
+# (24 MiB of float32 each: the two C5 images, 48 MiB each in full, stay under 64 MB together)
+DUMP_MAX_ELEMS = 6 * (1 << 20)
+
+
+def dump_outputs(path, outputs):
+    """Write each named array as path/<name>.npy (float32; the losses float64).  A larger
+    array is written as a fixed sample: its flattened elements at the sorted indices
+    numpy.random.default_rng(0).choice(size, DUMP_MAX_ELEMS, replace=False), the same for
+    every run of the same shape."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        a = np.ascontiguousarray(a)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def build_model(args, rank, local, world, ops_factory):
     """The product path train.py runs: ProgressiveGAN (pggan/model.py:11-265 interface)
     grown to the benchmark stage, reference init (W ~ N(0,1), b = 0), the resident
@@ -400,14 +439,17 @@ def main():
 
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     ops = _lib.HipOps(dtype)
-    timer = None if args.no_kernel_events else KernelTimer(ops, args.dtype)
+    # the per-kernel timers (and the eager last timed step that carries them): --full only
+    timer = KernelTimer(ops, args.dtype) if args.full and not args.no_kernel_events else None
     s, B = args.stage, args.batch
     depths = PAPER_DEPTHS
     R = 4 * 2 ** s
     model = build_model(args, rank, local, world, lambda dt: ops)
 
+    last = {}
+
     def step():
-        model.train_step()
+        last["out"] = model.train_step()
 
     log = lambda m: print(f"[bench] {m}", file=sys.stderr, flush=True)
     log(f"stage {s} batch {B} world {world}: {args.warmup} warm-up steps")
@@ -418,29 +460,36 @@ def main():
     # on the engine's own streams, under DP with the exchange's collectives and waits recorded
     # between the launch segments; --eager enqueues every step from Python
     model.use_replay = not args.eager and not args.graph
-    for _ in range(args.warmup):
+    # the timed steps are steady-state ones whatever --warmup says: the first two steps of a run
+    # are enqueued from Python (lazy buffers, weight packing), the third is recorded while it
+    # runs, later ones replay (--full runs its three host-enqueue steps before the timed loop
+    # instead)
+    n_warm = args.warmup if args.full else max(args.warmup, 3)
+    for _ in range(n_warm):
         step()
     model.flush()
     torch.cuda.synchronize()
-    # host-side cost of enqueueing one step (kernels are not waited for): if this is close
-    # to ms_per_step the step is launch-bound, not GPU-bound.  Measured on the steps the
-    # timed loop runs (graph replays in one process), before it.
-    # the first step after a flush starts without a deferred generator update (under DP a
-    # different replay key, whose second occurrence records): one step first, so the two
-    # measured below are the replays the timed loop runs
-    step()
-    hostparts = _host_breakdown() if os.environ.get("PG_BENCH_HOSTLOG") else None
-    h0 = time.perf_counter()
-    for _ in range(2):
+    host_ms = None
+    if args.full:
+        # host-side cost of enqueueing one step (kernels are not waited for): if this is close
+        # to ms_per_step the step is launch-bound, not GPU-bound.  Measured on the steps the
+        # timed loop runs (graph replays in one process), before it.
+        # the first step after a flush starts without a deferred generator update (under DP a
+        # different replay key, whose second occurrence records): one step first, so the two
+        # measured below are the replays the timed loop runs
         step()
-    model.flush()
-    host_ms = (time.perf_counter() - h0) * 1e3 / 2
-    if hostparts is not None:
-        hostparts.restore()
-        log("host enqueue per step (ms): " + ", ".join(
-            f"{k} {v[0] * 1e3 / 2:.3f} ({v[1] / 2:.1f}x)" for k, v in sorted(
-                hostparts.t.items(), key=lambda kv: -kv[1][0])))
-    torch.cuda.synchronize()
+        hostparts = _host_breakdown() if os.environ.get("PG_BENCH_HOSTLOG") else None
+        h0 = time.perf_counter()
+        for _ in range(2):
+            step()
+        model.flush()
+        host_ms = (time.perf_counter() - h0) * 1e3 / 2
+        if hostparts is not None:
+            hostparts.restore()
+            log("host enqueue per step (ms): " + ", ".join(
+                f"{k} {v[0] * 1e3 / 2:.3f} ({v[1] / 2:.1f}x)" for k, v in sorted(
+                    hostparts.t.items(), key=lambda kv: -kv[1][0])))
+        torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -468,6 +517,14 @@ def main():
     if timer:
         timer.on = False
     graph_steps = model.graph_replays - replays0
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller, before anything else runs on the GPU
+        img_real, img_fake = last["out"]
+        ld = model.loss_collector.loss_dict
+        dump_outputs(args.dump_outputs, {
+            "img_real": img_real.detach().float().cpu().numpy(),
+            "img_fake": img_fake.detach().float().cpu().numpy(),
+            "losses": torch.tensor([ld[k] for k in sorted(ld)], dtype=torch.float64).numpy()})
     # one more instrumented step (untimed) with every launch on one stream: the timed
     # region overlaps weight gradients (side stream) with the input-gradient chain, so its
     # per-launch durations include the other stream's contention; this gives each kernel
@@ -561,7 +618,7 @@ def main():
                     groups={k: _iso(k, v) for k, v in sorted(ksum_iso.items())})
         cpu = None
         log(f"timed: {1e3 * dt / args.steps:.3f} ms/step")
-        if args.cpu_baseline == "auto" and world == 1:
+        if args.full and args.cpu_baseline == "auto" and world == 1:
             log(f"CPU baseline: one oracle step on {args.cpu_threads or host_threads()} threads")
             cpu = cpu_baseline(args)
         line = {
@@ -589,9 +646,10 @@ def main():
                                     _engine_opts()["elide_zero_blend"] else ""),
                        "global_batch": B * world, "resolution": R,
                        "parallelism": f"dp{world}"},
-            "host_enqueue_ms_per_step": round(host_ms, 3),
+            # host_enqueue_ms_per_step, roofline, cpu_baseline: measured with --full, else null
+            "host_enqueue_ms_per_step": None if host_ms is None else round(host_ms, 3),
             # timed steps re-issued by the library's C++ replay (or a hipGraph with --graph);
-            # the last timed step runs eagerly with the per-launch timers
+            # with --full the last timed step runs eagerly with the per-launch timers
             "replayed_steps": graph_steps,
             "launch_path": ("hipgraph" if args.graph else "eager" if args.eager else
                             "cpp-replay"),
@@ -603,7 +661,8 @@ def main():
             line["dp_exchange"] = dict(
                 note="world-1 RCCL group: grad_ready buckets + side-stream joins on"
                 if world == 1 else "RCCL", bucket_mb=ex.bucket_bytes / (1 << 20),
-                collectives_per_step=round(ex.calls / (args.warmup + args.steps + 3), 1),
+                collectives_per_step=round(
+                    ex.calls / (n_warm + args.steps + (3 if args.full else 0)), 1),
                 host_ms_per_collective=round(1e3 * ex.host_s / max(ex.calls, 1), 3))
         print(json.dumps(line), flush=True)
     if dist.is_initialized():

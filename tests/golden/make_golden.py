@@ -9,7 +9,8 @@ and ``torch.randn`` fed the same synthetic inputs, then the reference's own
 ``ProgressiveGAN.train_step`` (pggan/model.py:206-255) is called.
 
 Output: tests/golden/<config>.npz  (inputs are NOT stored: they are regenerated
-from the seeds; outputs, losses, gradients and post-Adam parameters are).
+from the seeds; outputs, losses, gradients and post-Adam parameters are), continued
+in <config>.partK.npz where one file would pass 1 MiB (save_parts).
 
 Usage:  python tests/golden/make_golden.py [config-name ...]
 """
@@ -299,8 +300,108 @@ def run_schedule(R, n_steps=30):
     return np.array(rows, np.float64)
 
 
+PART_BYTES = 900_000   # a committed fixture file stays under 1 MiB
+
+
+def save_parts(name, out):
+    """Write the arrays as <name>.npz and, when they do not fit PART_BYTES compressed,
+    continuation files <name>.part1.npz, ... (tests/golden_utils.load reads them back as one
+    fixture); arrays keep their order, stale continuation files are removed.  Returns the
+    paths written."""
+    import glob
+    import zlib
+    for p in glob.glob(os.path.join(HERE, name + ".part*.npz")):
+        os.remove(p)
+    parts, size = [{}], 0
+    for k, a in out.items():
+        n = len(zlib.compress(np.ascontiguousarray(a).tobytes(), 6)) + 2 * len(k) + 200
+        if parts[-1] and size + n > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = a
+        size += n
+    paths = []
+    for i, d in enumerate(parts):
+        paths.append(os.path.join(HERE, name + (f".part{i}.npz" if i else ".npz")))
+        np.savez_compressed(paths[-1], **d)
+    return paths
+
+
+def ref_model(R, save_root, run_id, s, ckpt_id=None, depths=None, latent_dim=None):
+    """The reference's ProgressiveGAN at stage s (default: tiny depths, its own latent size), on
+    the CPU, ready for its own train_step / save_checkpoint / load_checkpoint."""
+    from gen_inputs import TINY_DEPTHS
+    depths = list(depths or TINY_DEPTHS)
+    args = R["Config"].from_yaml(os.path.join(REF, "configs.yaml"))
+    args.beta1 = float(args.beta1)
+    args.isMaster = False
+    args.depths = list(depths)
+    if latent_dim:
+        args.latent_dim = latent_dim
+    args.batch_per_gpu = 4
+    args.save_root = str(save_root)
+    args.run_id = run_id
+    args.ckpt_id = ckpt_id
+    args.ckpt_step = None
+    m = object.__new__(R["ProgressiveGAN"])
+    m.args, m.gpu, m.scale_index = args, "cpu", s
+    m.G = R["Generator"](args.latent_dim, depths[0], args.init_bias_to_zero, args.LReLU_slope,
+                         args.apply_pixel_norm, args.generator_last_activation, args.output_dim,
+                         args.equalized_lr)
+    m.D = R["Discriminator"](depths[0], args.init_bias_to_zero, args.LReLU_slope,
+                             args.decision_layer_size, args.apply_minibatch_norm, args.input_dim,
+                             args.equalized_lr)
+    for net in (m.G, m.D):     # the reference calls .cuda() after add_block (CPU here)
+        net.cuda = (lambda n: (lambda *a, **k: n))(net)
+    for i in range(1, s + 1):
+        m.G.add_block(depths[i])
+        m.D.add_block(depths[i])
+    m.set_optimizers()
+    m._loss_collector = R["WGANGPLoss"](args)
+    m.alpha_index, m.alpha_jump_value = 1, 0.5
+    m.next_alpha_jump_step, m.next_scale_jump_step = 9, 12
+    return m
+
+
+REF_CKPT_STEP = 7   # the global step of the reference checkpoint
+# the stored checkpoint (tests/golden/ref_ckpt): narrow enough for two small files
+REF_CKPT_DEPTHS = [16, 8, 8, 8, 8, 8, 8, 8, 8]
+REF_CKPT_LATENT = 32
+
+
+def run_ref_checkpoint(R, save_root, run_id="ref", depths=None, latent_dim=None):
+    """The reference trains one step at stage 1 (alpha 0.5, seeded parameters and inputs) and
+    writes {save_root}/{run_id}/ckpt/{G,D}_{7,latest}.pt with its own save_checkpoint
+    (pggan/model.py:50-67, lib/checkpoint.py:22-34); returns the reference model."""
+    torch.manual_seed(3)
+    mr = ref_model(R, save_root, run_id, 1, depths=depths, latent_dim=latent_dim)
+    PG = make_params([(k, tuple(v.shape)) for k, v in mr.G.state_dict().items()], seed=41)
+    PD = make_params([(k, tuple(v.shape)) for k, v in mr.D.state_dict().items()], seed=42)
+    mr.G.load_state_dict({k: torch.from_numpy(v) for k, v in PG.items()})
+    mr.D.load_state_dict({k: torch.from_numpy(v) for k, v in PD.items()})
+    mr.G.alpha = mr.D.alpha = 0.5
+    st = make_inputs(4, 8, seed=43)[0]
+    mr.load_next_batch = lambda: torch.from_numpy(st["real"])
+    mr.train_step()
+    mr.save_checkpoint(REF_CKPT_STEP)
+    return mr
+
+
 def main(names):
     R = import_reference()
+    if not names or "ref_ckpt" in names:
+        # tests/golden/ref_ckpt/ckpt/{G,D}_latest.pt: what the reference's save_checkpoint wrote
+        # (the {G,D}_7.pt twins hold the same bytes and are not kept); written from inside
+        # tests/golden with save_root "." so that the stored args name no directory of the host
+        cwd = os.getcwd()
+        os.chdir(HERE)
+        try:
+            run_ref_checkpoint(R, ".", "ref_ckpt", REF_CKPT_DEPTHS, REF_CKPT_LATENT)
+            for n in "GD":
+                os.remove(os.path.join("ref_ckpt", "ckpt", f"{n}_{REF_CKPT_STEP}.pt"))
+        finally:
+            os.chdir(cwd)
+        print("ref_ckpt: written")
     if not names or "schedule" in names:
         np.savez_compressed(os.path.join(HERE, "schedule.npz"), rows=run_schedule(R),
                             meta=np.frombuffer(repr(SCHEDULE_ARGS).encode(), dtype=np.uint8))
@@ -317,9 +418,9 @@ def main(names):
         if names and name not in names:
             continue
         out = run_config(R, name, depths, s, B, alpha, n_steps, full)
-        path = os.path.join(HERE, name + ".npz")
-        np.savez_compressed(path, **out)
-        print(f"{name}: {len(out)} arrays, {os.path.getsize(path) / 1e6:.2f} MB")
+        paths = save_parts(name, out)
+        print(f"{name}: {len(out)} arrays, {len(paths)} file(s), "
+              f"{sum(os.path.getsize(p) for p in paths) / 1e6:.2f} MB")
 
 
 if __name__ == "__main__":

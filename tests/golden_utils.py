@@ -7,8 +7,28 @@ import numpy as np
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
+class Fixture:
+    """The arrays of one fixture: <name>.npz and, where that file alone would pass 1 MiB, its
+    continuation files <name>.part1.npz, ... (tests/golden/make_golden.save_parts).  Offers
+    what the tests use of an NpzFile: `files`, `key in z`, `z[key]`."""
+
+    def __init__(self, parts):
+        self._where = {k: z for z in parts for k in z.files}
+        self.files = list(self._where)
+
+    def __contains__(self, key):
+        return key in self._where
+
+    def __getitem__(self, key):
+        return self._where[key][key]
+
+
 def load(name):
-    z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    parts = [np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)]
+    while os.path.exists(os.path.join(GOLDEN, f"{name}.part{len(parts)}.npz")):
+        parts.append(np.load(os.path.join(GOLDEN, f"{name}.part{len(parts)}.npz"),
+                             allow_pickle=False))
+    z = Fixture(parts)
     meta = ast.literal_eval(bytes(z["meta"]).decode())
     return meta, z
 

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 run() {
   local name=$1; shift
-  timeout -k 10 300 python bench.py --steps 10 --warmup 3 --cpu-baseline off "$@" \
+  timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --cpu-baseline off "$@" \
     > "gpurun_out/cfg_$name.log" 2>&1
   local rc=$?
   echo "$name rc=$rc"

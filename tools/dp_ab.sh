@@ -14,7 +14,7 @@ rounds=${ROUNDS:-2}
 : > gpurun_out/dp_ab.log
 run() {
   local name=$1; shift
-  env "$@" timeout -k 10 300 python bench.py --steps 10 --warmup 3 --cpu-baseline off --no-kernel-events \
+  env "$@" timeout -k 10 300 python bench.py --full --steps 10 --warmup 3 --cpu-baseline off --no-kernel-events \
     $ARGS > gpurun_out/dp_ab.json 2> gpurun_out/dp_ab.err
   local rc=$?
   [ $rc -eq 0 ] || { echo "bench $name failed"; tail -5 gpurun_out/dp_ab.err; exit $rc; }
