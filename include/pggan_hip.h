@@ -391,6 +391,18 @@ int pg_adam_table(float lr, float beta1, float beta2, int tlen, float* host_tabl
 int pg_adam_dev(size_t n, float* p, const float* g, float* m, float* v, float beta1, float beta2,
                 float eps, const float* table, int tlen, int* step, void* stream);
 
+/* pg_adam / pg_adam_dev with the generator's weight average updated in the same launch:
+ * p, m, v exactly as the entry above writes them, then, from the new p still in its register,
+ * ema[i] += one_minus_decay * (p[i] - ema[i]) in fp32 (`ema` DEVICE, n floats, laid out as p;
+ * one_minus_decay = (float)(1.0 - (double)decay), in (0, 1]).  PG_ERR_ARG on a null pointer or
+ * a coefficient outside that range. */
+int pg_adam_ema(size_t n, float* p, const float* g, float* m, float* v, float* ema,
+                float one_minus_decay, float lr, float beta1, float beta2, float eps, int step,
+                void* stream);
+int pg_adam_dev_ema(size_t n, float* p, const float* g, float* m, float* v, float* ema,
+                    float one_minus_decay, float beta1, float beta2, float eps, const float* table,
+                    int tlen, int* step, void* stream);
+
 /* ---- N(0,1) latents (counter-based, deterministic in (seed, offset)) */
 int pg_randn(size_t n, uint64_t seed, uint64_t offset, float* out, void* stream);
 /* the same draw with the offset in DEVICE memory; *offset then advances by n (graph replay) */

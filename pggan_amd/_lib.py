@@ -160,6 +160,8 @@ _SIGS = {
     "pg_adam_table_len": ([_F, _F, _F], _I),
     "pg_adam_table": ([_F, _F, _F, _I, _VP], _I),
     "pg_adam_dev": ([_SZ, _VP, _VP, _VP, _VP, _F, _F, _F, _VP, _I, _VP, _VP], _I),
+    "pg_adam_ema": ([_SZ, _VP, _VP, _VP, _VP, _VP, _F, _F, _F, _F, _F, _I, _VP], _I),
+    "pg_adam_dev_ema": ([_SZ, _VP, _VP, _VP, _VP, _VP, _F, _F, _F, _F, _VP, _I, _VP, _VP], _I),
     "pg_cast": ([_I, _I, _SZ, _VP, _VP, _VP], _I),
     "pg_augment_workspace_bytes": ([_I, _I, _I], _SZ),
     "pg_augment_u8": ([_I, _I, _I, _VP, _VP, _VP, _SZ, _VP, _VP], _I),
@@ -208,6 +210,11 @@ def _p(t):
     if t is None:
         return None
     return ctypes.c_void_p(t.data_ptr())
+
+
+def one_minus_decay(decay):
+    """The weight average's coefficient as the kernels take it: (float)(1.0 - (double)decay)."""
+    return ctypes.c_float(1.0 - float(decay)).value
 
 
 class HipEvent:
@@ -739,6 +746,21 @@ class HipOps:
         tab, n = self.adam_table(lr, beta1, beta2, p.device)
         self._chk(self.lib.pg_adam_dev(p.numel(), _p(p), _p(g), _p(m), _p(v), beta1, beta2, eps,
                                        _p(tab), n, _p(step_dev), self._s()), "adam_dev")
+
+    def adam_ema(self, p, g, m, v, ema, *, decay, lr, beta1, beta2, eps, step):
+        """adam() plus the weight average in the same launch: ema += (1 - decay) * (p - ema)."""
+        self._cuda(p, g, m, v, ema)
+        self._chk(self.lib.pg_adam_ema(p.numel(), _p(p), _p(g), _p(m), _p(v), _p(ema),
+                                       one_minus_decay(decay), lr, beta1, beta2, eps, step,
+                                       self._s()), "adam_ema")
+
+    def adam_dev_ema(self, p, g, m, v, ema, *, decay, lr, beta1, beta2, eps, step_dev):
+        """adam_dev() plus the weight average in the same launch: replayable like it."""
+        self._cuda(p, g, m, v, ema, step_dev)
+        tab, n = self.adam_table(lr, beta1, beta2, p.device)
+        self._chk(self.lib.pg_adam_dev_ema(p.numel(), _p(p), _p(g), _p(m), _p(v), _p(ema),
+                                           one_minus_decay(decay), beta1, beta2, eps, _p(tab), n,
+                                           _p(step_dev), self._s()), "adam_dev_ema")
 
     def randn_dev(self, out, seed, offset_dev):
         """pg_randn with the offset in device memory (advanced by out.numel())."""

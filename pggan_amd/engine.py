@@ -103,9 +103,13 @@ def dead_params(net, s):
 
 class FlatParams:
     """fp32 parameters of one net in one flat buffer (live parameters first) plus
-    flat gradient / Adam-moment buffers; `views[name]` are reference-shaped views."""
+    flat gradient / Adam-moment buffers; `views[name]` are reference-shaped views.
 
-    def __init__(self, shapes, dead, device, init=None):
+    `ema` (the generator's weight average, on request; None otherwise) is one more flat fp32
+    buffer with the layout of `flat`, `eviews[name]` its views: it starts as a copy of the
+    parameters and StepEngine.adam updates its live range in the Adam launch."""
+
+    def __init__(self, shapes, dead, device, init=None, ema=False):
         order = [n for n, _ in shapes if n not in dead] + [n for n, _ in shapes if n in dead]
         shp = dict(shapes)
         self.names = [n for n, _ in shapes]          # reference order
@@ -137,6 +141,8 @@ class FlatParams:
         if init is not None:
             for n in self.names:
                 self.views[n].copy_(init[n])
+        self.ema = self.flat.clone() if ema else None
+        self.eviews = {n: self._view(self.ema, n) for n in self.names} if ema else {}
 
     def _view(self, buf, n):
         o = self.offsets[n]
@@ -164,6 +170,7 @@ class Hyper:
     gp_mode: str = "r1"         # "r1" (live reference path) | "wgan-gp" (optional mode)
     W_gp: float = 10.0
     W_drift: float = 0.0        # W_drift_D (wgan-gp mode only, pggan/loss.py:94-100)
+    ema_decay: float = 0.0      # decay of G's weight average (FlatParams.ema); 0: off
 
 
 # measurement only (bench.py's isolated instrumented step): run the side-stream launches
@@ -1626,17 +1633,30 @@ class StepEngine:
         else:
             self._side_join()
         n = fp.n_live
-        if hasattr(self.ops, "adam_dev"):
+        # the weight average (G only: D's FlatParams has no ema buffer) rides in the Adam
+        # launch over the same live range, so dead parameters keep their average as Adam
+        # keeps their value; an op set without the fused entries (the CPU test double) gets
+        # the plain update followed by the same recursion
+        ema = fp.ema is not None and hp.ema_decay > 0
+        dev = hasattr(self.ops, "adam_dev")
+        fused = ema and hasattr(self.ops, "adam_dev_ema" if dev else "adam_ema")
+        bufs = [fp.flat[:n], fp.grad[:n], fp.m[:n], fp.v[:n]]
+        kw = dict(lr=lr, beta1=hp.beta1, beta2=hp.beta2, eps=hp.eps)
+        if fused:
+            bufs.append(fp.ema[:n])
+            kw["decay"] = hp.ema_decay
+        if dev:
             if fp._step_dev_host != fp.step:   # a reset / checkpoint load changed the count
                 fp.step_dev.fill_(fp.step)
             fp.step += 1
             fp._step_dev_host = fp.step
-            self.ops.adam_dev(fp.flat[:n], fp.grad[:n], fp.m[:n], fp.v[:n], lr=lr, beta1=hp.beta1,
-                              beta2=hp.beta2, eps=hp.eps, step_dev=fp.step_dev)
-            return
-        fp.step += 1
-        self.ops.adam(fp.flat[:n], fp.grad[:n], fp.m[:n], fp.v[:n], lr=lr, beta1=hp.beta1,
-                      beta2=hp.beta2, eps=hp.eps, step=fp.step)
+            (self.ops.adam_dev_ema if fused else self.ops.adam_dev)(*bufs, step_dev=fp.step_dev,
+                                                                    **kw)
+        else:
+            fp.step += 1
+            (self.ops.adam_ema if fused else self.ops.adam)(*bufs, step=fp.step, **kw)
+        if ema and not fused:
+            fp.ema[:n].lerp_(fp.flat[:n], L.one_minus_decay(hp.ema_decay))
 
     def train_step(self, real, z1, z2, alpha_G, alpha_D, grad_hook=None, gp_eps=None):
         """One full step: D half (R1) + Adam_D, G half + Adam_G (pggan/model.py:206-255).

@@ -14,6 +14,9 @@ Differences (deliberate):
   * set_multi_GPU really all-reduces G and D gradients (mean over ranks) before
     each Adam step; the reference discards its DDP wrapper (lib/model.py:78-79).
   * latents are drawn on the GPU per rank (pg_randn) instead of the CPU RNG.
+  * config `ema_decay` (blank: off) keeps `G_ema`, the exponential moving average of G's
+    weights the paper samples from (the reference dropped it): updated inside the Adam_G
+    launch, sampled by `sample(z)`, saved beside the reference's files as `G_ema_*.pt`.
 """
 from __future__ import annotations
 
@@ -115,7 +118,12 @@ class ProgressiveGAN:
                              slope_cfg=float(cfg_get(args, "LReLU_slope", 0.2)),
                              gp_mode=cfg_get(args, "gp_mode", "r1"),
                              W_gp=float(cfg_get(args, "W_gp", 10)),
-                             W_drift=float(cfg_get(args, "W_drift_D", 0) or 0))
+                             W_drift=float(cfg_get(args, "W_drift_D", 0) or 0),
+                             ema_decay=float(cfg_get(args, "ema_decay", 0) or 0))
+        if not 0.0 <= self.hyper.ema_decay < 1.0:
+            raise ValueError(f"ema_decay must be in (0, 1), or blank / 0 for off: "
+                             f"{self.hyper.ema_decay}")
+        self.G_ema = None
         self._engines = {}
         self._rng_step = 0
         self.global_step = 0
@@ -140,6 +148,28 @@ class ProgressiveGAN:
         self.D.compute_dtype = self.dtype
         self.G.train()
         self.D.train()
+        if self.hyper.ema_decay > 0:
+            # the averaged generator: G's architecture and weights; its parameters become
+            # views of fpG.ema in set_optimizers.  Built without touching the global RNG, so
+            # a run draws the same initial weights with the average on or off.
+            with torch.random.fork_rng(devices=[]):
+                self.G_ema = Generator(a.latent_dim, a.depths[0], a.init_bias_to_zero,
+                                       a.LReLU_slope, a.apply_pixel_norm,
+                                       a.generator_last_activation, a.output_dim,
+                                       a.equalized_lr).to(self.device)
+            self.G_ema.compute_dtype = self.dtype
+            self.G_ema.load_state_dict(self.G.state_dict())
+            self.G_ema.eval().requires_grad_(False)
+
+    def _ema_add_blocks(self):
+        """G_ema grows with G (change_scale, load_checkpoint, or blocks added to G directly);
+        the new block's values are set from G when the flat buffers are rebuilt."""
+        if self.G_ema is None:
+            return
+        with torch.random.fork_rng(devices=[]):
+            for d in self.G.block_depths[len(self.G_ema.block_depths):]:
+                self.G_ema.add_block(d)
+        self.G_ema.requires_grad_(False)
 
     def set_multi_GPU(self):
         """lib/model.py:74-79 + lib/utils.py:78-83, but with a working gradient all-reduce:
@@ -172,6 +202,8 @@ class ProgressiveGAN:
             for net in (self.G, self.D):
                 for p in net.parameters():
                     dist.broadcast(p.data, 0)
+            if getattr(getattr(self, "fpG", None), "ema", None) is not None:
+                dist.broadcast(self.fpG.ema, 0)
             self._params_changed()
 
     def _params_changed(self):
@@ -181,10 +213,22 @@ class ProgressiveGAN:
     def _flat(self, net, which):
         shapes = [(n, tuple(p.shape)) for n, p in net.named_parameters()]
         init = {n: p.detach() for n, p in net.named_parameters()}
-        fp = E.FlatParams(shapes, E.dead_params(which, self.scale_index), self.device, init)
+        ema = which == "G" and self.G_ema is not None
+        fp = E.FlatParams(shapes, E.dead_params(which, self.scale_index), self.device, init,
+                          ema=ema)
         for n, p in net.named_parameters():
             p.data = fp.views[n]
             p.grad = fp.gviews[n]
+        if ema:
+            # the average is not optimizer state: names that existed keep their values bit
+            # for bit through the new live-first order, new ones (the added block and its
+            # toRGB; everything at the first call) start as G's, which FlatParams copied
+            self._ema_add_blocks()
+            old = getattr(getattr(self, "fpG", None), "eviews", {})
+            for n, p in self.G_ema.named_parameters():
+                if n in old:
+                    fp.eviews[n].copy_(old[n])
+                p.data = fp.eviews[n]
         return fp
 
     def set_optimizers(self):
@@ -350,7 +394,8 @@ class ProgressiveGAN:
         return ("replay" if self.use_replay else "graph",
                 id(eng), id(self.fpG), id(self.fpD), B, float(self.G.alpha), float(self.D.alpha),
                 h.lr_G, h.lr_D, h.beta1, h.beta2, h.eps, h.W_adv, h.slope_cfg, h.gp_mode, h.W_gp,
-                h.W_drift, id(self._exchange), isinstance(eng._pending_G, DP.Handle))
+                h.W_drift, id(self._exchange), isinstance(eng._pending_G, DP.Handle),
+                h.ema_decay)
 
     def _step_body(self, eng, real, B):
         """The work of one step after the batch is resident: latents, then the engine step."""
@@ -482,6 +527,8 @@ class ProgressiveGAN:
         if ver != getattr(self, "_param_ver", ver):
             self._params_changed()
         self._param_ver = ver
+        if self.G_ema is not None:
+            self.G_ema.alpha = self.G.alpha
         self.hyper.lr_G, self.hyper.lr_D = self.opt_G.lr, self.opt_D.lr
         z = getattr(self, "_z", None)
         if z is None or z.shape[1] != B:
@@ -496,6 +543,20 @@ class ProgressiveGAN:
         img_real, _, img_fake = out
         self.loss_collector.attach(eng.loss, self.hyper.gp_mode)
         return [img_real, img_fake]
+
+    def sample(self, z, ema=True):
+        """Images for latents z from the averaged generator (ema=True: what the paper shows)
+        or from G itself, at G's current alpha, on the forward-only sampling engine."""
+        if ema and self.G_ema is None:
+            raise RuntimeError("sample(ema=True): the weight average is off (config ema_decay "
+                               "is blank or 0); set it, e.g. 0.999, or pass ema=False")
+        self.flush()
+        net = self.G
+        if ema:
+            net = self.G_ema
+            net.alpha = self.G.alpha
+        with torch.no_grad():
+            return net(z)
 
     # ------------------------------------------------------------------ schedule
     def reset_solver(self):
@@ -524,6 +585,7 @@ class ProgressiveGAN:
         self.next_scale_jump_step += self.args.max_step_at_scale[self.scale_index]
         self.G.add_block(self.args.depths[self.scale_index])
         self.D.add_block(self.args.depths[self.scale_index])
+        self._ema_add_blocks()
         self._broadcast_params()
         self.reset_solver()
         self.reset_alpha(global_step)
@@ -572,6 +634,8 @@ class ProgressiveGAN:
         base = self._ckpt_dict(global_step)
         checkpoint.save_checkpoint(self.G, self.opt_G, "G", dict(base))
         checkpoint.save_checkpoint(self.D, self.opt_D, "D", dict(base))
+        if self.G_ema is not None:
+            checkpoint.save_ema_checkpoint(self.G_ema, self.hyper.ema_decay, dict(base))
 
     def load_checkpoint(self):
         """pggan/model.py:70-101: restore schedule scalars, re-add blocks, fresh solver, then
@@ -581,9 +645,14 @@ class ProgressiveGAN:
         Dd = checkpoint.load_checkpoint(self.args, "D", self.device)
         if not Gd or not Dd:
             raise RuntimeError("checkpoint not found")
+        # G_ema_*.pt beside the reference's files (read before the saved args replace ours)
+        Ed = checkpoint.load_checkpoint(self.args, "G_ema", self.device) \
+            if self.G_ema is not None else 0
         for k, v in Gd["args"].items():
             setattr(self.args, k, v) if not hasattr(self.args, "__setitem__") else \
                 self.args.__setitem__(k, v)
+        if self.G_ema is not None:     # the average is this run's choice, not the saved one's
+            self.args.ema_decay = self.hyper.ema_decay
         self.global_step = Gd["global_step"]
         self.alpha_index = Gd["alpha_index"]
         self.alpha_jump_value = Gd["alpha_jump_value"]
@@ -603,6 +672,14 @@ class ProgressiveGAN:
         self.D.load_state_dict(Dd["model"], strict=False)
         self.opt_G.load_state_dict(Gd["optimizer"])
         self.opt_D.load_state_dict(Dd["optimizer"])
+        if self.G_ema is not None:
+            # a checkpoint without the file (made by the reference, or with the average off)
+            # starts the average from the loaded G
+            self.G_ema.alpha = self.G.alpha
+            if Ed:
+                self.G_ema.load_state_dict(Ed["model"], strict=False)
+            else:
+                self.fpG.ema.copy_(self.fpG.flat)
         self._params_changed()
 
     def save_image(self, images, step):

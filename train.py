@@ -62,6 +62,13 @@ def train(args):
         model.next_alpha_jump_step = args.alpha_jump_start[0]
     step = model.global_step if resumed else 0
     max_step = min(sum(args.max_step_at_scale), args.max_step)
+    fixed_z = None
+    if rank == 0 and model.G_ema is not None:
+        # the averaged generator on 8 fixed latents: a third row of every saved grid (as
+        # wide as the other two, which show the first 8 images of a batch)
+        gen = torch.Generator().manual_seed(1234)
+        fixed_z = torch.randn(min(8, args.batch_per_gpu), args.latent_dim,
+                              generator=gen).to(model.device)
     while step < max_step:
         model.check_jump(step)
         images = model.train_step()
@@ -69,6 +76,8 @@ def train(args):
             if step % args.loss_cycle == 0:
                 model.loss_collector.print_loss(step)
             if step % args.test_cycle == 0:
+                if fixed_z is not None:
+                    images = list(images) + [model.sample(fixed_z)]
                 model.save_image(images, step)
             if step % args.ckpt_cycle == 0:
                 model.save_checkpoint(step)
