@@ -26,6 +26,7 @@ images NCHW fp32, parameters/gradients/Adam state fp32 in flat buffers.
 from __future__ import annotations
 
 import contextlib
+import functools
 import math
 import os
 from dataclasses import dataclass
@@ -191,8 +192,8 @@ ENGINE_DEFAULTS = dict(
     fuse_pnbwd=True,       # G PixelNorm backward in the input-gradient conv epilogue
     fuse_pn_pool=True,     # ... also after the pool of the next level's conv-a input gradient
     fuse_rgb_pnbwd=True,   # the toRGB input gradient with the top PixelNorm backward
-    fuse_dbits=True,       # D conv+lrelu+pool outputs as sign bits (see _dbits)
-    dbits_min_res=512,     # ... from this resolution; below it the unpool-pass bits (_ubits)
+    fuse_dbits=True,       # D conv+lrelu+pool outputs as sign bits (see _dmode)
+    dbits_min_res=512,     # ... from this resolution; below it the unpool-pass bits ("ubits")
     fuse_ubits=True,
     fuse_rgbbits=True,     # the top fromRGB output's sign bits (see _rgbbits)
     # DP: the G all-reduce behind the next step's real-image part (-1: only where the exchange
@@ -226,6 +227,18 @@ def engine_options(overrides=None):
     return opts
 
 
+def _memo(fn):
+    """A fusion predicate of StepEngine, decided once per argument tuple at its first use: the
+    tests and the A/B tools set options after construction and before the first step."""
+    @functools.wraps(fn)
+    def decided(self, *args):
+        key = (fn.__name__,) + args
+        if key not in self._decided:
+            self._decided[key] = fn(self, *args)
+        return self._decided[key]
+    return decided
+
+
 class StepEngine:
     """All device buffers and kernel schedules for one (stage, batch, dtype)."""
 
@@ -246,7 +259,8 @@ class StepEngine:
         for k, v in engine_options(options).items():
             setattr(self, k, v)
         self.ws = None          # split-K workspace (fp32), grown on first use
-        self._ws_cache = {}
+        self._ws_cache = {}     # workspace bytes per launch shape (_ws_bytes)
+        self._decided = {}      # fusion predicates (_memo)
         self.plan = None        # pg_step_plan description (HIP library)
         if forward_only is None and hasattr(ops, "step_plan"):
             # the step's split-reduction workspace at once (pg_step_plan_workspace_size), so
@@ -471,12 +485,9 @@ class StepEngine:
             D["u2"] = t(B, f32=True)
             D["hl"] = t(B, f32=True)
             D["gimg"] = t(B, 3, R, R, f32=True)
-            D["gbar"] = t(B, 3, R, R, f32=True)
-            D["real"] = t(B, 3, R, R, f32=True)
             if s >= 1:
                 D["real_in"] = t(B, 3, R, R, f32=True)
             # WGAN-GP optional mode
-            D["interp"] = t(B, 3, R, R, f32=True)
             D["gp_eps"] = t(B, 1, f32=True)
             D["gp_c"] = t(B, 1, f32=True)         # 1 - eps
             # per-sample squared norms of dD/dx (kept at zero between uses: pg_penalty_scale
@@ -644,17 +655,6 @@ class StepEngine:
         """Whether the final pass's last weight gradients run on the main stream."""
         return self.side is not None and not FORCE_SERIAL and self.tail_main
 
-    def _tail_wait(self):
-        """Before a main-stream weight gradient of the final pass: the side-stream launches
-        issued before this pass (the tangent's weight terms it accumulates onto) are done."""
-        ev, self._tail_ev = getattr(self, "_tail_ev", None), None
-        if ev is not None:
-            cur = torch.cuda.current_stream()
-            if isinstance(ev, torch.cuda.Event):
-                cur.wait_event(ev)
-            else:
-                ev.wait(cur)
-
     def _ready_main(self, net, *prefixes):
         """grad_ready for gradients written on the main stream: the callbacks run on the
         side stream (_ready), which first waits for the main one."""
@@ -664,6 +664,7 @@ class StepEngine:
             self._side_wait_main()
         self._ready(net, *prefixes)
 
+    @_memo
     def _conv_sup(self):
         """ops.conv_supported at every batch size the D passes run (B, and 2B when the D
         half's passes are merged): a sign-bit layout decided once serves both."""
@@ -673,141 +674,117 @@ class StepEngine:
         Bs = self._Bs
         return lambda B, **kw: all(f(B=b, **kw) for b in Bs)
 
+    @_memo
+    def _dmode(self, i):
+        """What D level i keeps of its conv-b (conv + lrelu + pool) pre-pool output for the
+        lrelu' mask of the backward passes:
+          "bits"   sign bits only, and every consumer of the mask (input-gradient conv, weight
+                   gradient, R1 tangent) reads the bits and the pooled-resolution gradient
+                   directly (no unpool_mask pass).  From dbits_min_res: below 512^2 the saved
+                   bytes no longer pay for the masking work in the staging.
+          "ubits"  sign bits too, where the pooled conv supports it (the wide LDS-DMA tile at
+                   64^2-256^2): the input-gradient pass forms gzb = up2(g) * lrelu'(bits) in
+                   the unpool pass (pg_unpool_mask_bits), the R1 tangent masks and pools in its
+                   conv (no avgpool launch); gzb itself stays materialised for the
+                   input-gradient conv and the weight gradient.
+          "act"    the full-resolution activation (bf{i})."""
+        f = self._conv_sup()
+        d, Ri, B = self.depths, 8 * 2 ** i, self.B
+        if not (self.fuse_dbits and f is not None and d[i] % 16 == 0):
+            return "act"
+
+        def sup(cin, cout, flags):
+            return f(B=B, H=Ri, W=Ri, cin=cin, cout=cout, flags=flags)
+        fwd = L.CONV_BIAS | L.CONV_LRELU | L.CONV_POOL | L.CONV_Y2_BITS
+        tan = L.CONV_MASK | L.CONV_AUX_BITS | L.CONV_POOL
+        if (Ri >= self.dbits_min_res and sup(d[i + 1], d[i], fwd) and
+                sup(d[i], d[i + 1], L.CONV_UPS_IN | L.CONV_X_BITS | L.CONV_MASK) and
+                sup(d[i + 1], d[i], tan) and sup(d[i + 1], d[i], L.CONV_GZ_BITS)):
+            return "bits"
+        if self.fuse_ubits and sup(d[i + 1], d[i], fwd) and sup(d[i + 1], d[i], tan):
+            return "ubits"
+        return "act"
+
     def _dbits(self, i):
-        """Whether D level i keeps its conv-b (conv + lrelu + pool) output as sign bits only:
-        the forward writes bits instead of the full-resolution activation, and every consumer
-        of its lrelu' mask (input-gradient conv, weight gradient, R1 tangent) reads the bits
-        and the pooled-resolution gradient directly (no unpool_mask pass)."""
-        key = ("dbits", i, 0, 0, 0)
-        if key not in self._ws_cache:
-            f = self._conv_sup()
-            d, Ri = self.depths, 8 * 2 ** i
-            # below 512^2 the saved bytes no longer pay for the masking work in the staging
-            ok = bool(self.fuse_dbits and f is not None and d[i] % 16 == 0 and
-                      Ri >= self.dbits_min_res)
-            if ok:
-                B = self.B
-                ok = (f(B=B, H=Ri, W=Ri, cin=d[i + 1], cout=d[i],
-                        flags=L.CONV_BIAS | L.CONV_LRELU | L.CONV_POOL | L.CONV_Y2_BITS)
-                      and f(B=B, H=Ri, W=Ri, cin=d[i], cout=d[i + 1],
-                            flags=L.CONV_UPS_IN | L.CONV_X_BITS | L.CONV_MASK)
-                      and f(B=B, H=Ri, W=Ri, cin=d[i + 1], cout=d[i],
-                            flags=L.CONV_MASK | L.CONV_AUX_BITS | L.CONV_POOL)
-                      and f(B=B, H=Ri, W=Ri, cin=d[i + 1], cout=d[i], flags=L.CONV_GZ_BITS))
-            self._ws_cache[key] = ok
-        return self._ws_cache[key]
+        return self._dmode(i) == "bits"
 
     def _ubits(self, i):
-        """Below the sign-bit resolution (_dbits false): D level i's conv b still keeps its
-        pre-pool lrelu sign as bits instead of the bf16 activation where the pooled conv
-        supports it (the wide LDS-DMA tile at 64^2-256^2): the input-gradient pass forms
-        gzb = up2(g) * lrelu'(bits) in the unpool pass (pg_unpool_mask_bits), the R1 tangent
-        masks and pools in its conv (no avgpool launch); gzb itself stays materialised for the
-        input-gradient conv and the weight gradient."""
-        key = ("ubits", i, 0, 0, 0)
-        if key not in self._ws_cache:
-            f = self._conv_sup()
-            d, Ri, B = self.depths, 8 * 2 ** i, self.B
-            ok = bool(f is not None and self.fuse_dbits and self.fuse_ubits and
-                      not self._dbits(i) and d[i] % 16 == 0)
-            if ok:
-                ok = (f(B=B, H=Ri, W=Ri, cin=d[i + 1], cout=d[i],
-                        flags=L.CONV_BIAS | L.CONV_LRELU | L.CONV_POOL | L.CONV_Y2_BITS)
-                      and f(B=B, H=Ri, W=Ri, cin=d[i + 1], cout=d[i],
-                            flags=L.CONV_MASK | L.CONV_AUX_BITS | L.CONV_POOL))
-            self._ws_cache[key] = ok
-        return self._ws_cache[key]
+        return self._dmode(i) == "ubits"
 
+    @_memo
     def _rgbbits(self):
         """Whether the top fromRGB layer also writes the sign bits of its output and its two
         lrelu' consumers -- the input gradient of the top conv a and the fromRGB tangent --
         mask from those bits instead of the bf16 activation (at >= the sign-bit resolution)."""
-        key = ("rgbbits", 0, 0, 0, 0)
-        if key not in self._ws_cache:
-            f = self._conv_sup()
-            d, s, R, B = self.depths, self.s, self.R, self.B
-            ok = bool(f is not None and self.fuse_dbits and self.fuse_rgbbits and s >= 1 and
-                      d[s] % 8 == 0 and
-                      d[s] <= 64 and R >= self.dbits_min_res and
-                      f(B=B, H=R, W=R, cin=d[s], cout=d[s], flags=L.CONV_MASK | L.CONV_AUX_BITS))
-            self._ws_cache[key] = ok
-        return self._ws_cache[key]
+        f = self._conv_sup()
+        d, s, R, B = self.depths, self.s, self.R, self.B
+        return bool(f is not None and self.fuse_dbits and self.fuse_rgbbits and s >= 1 and
+                    d[s] % 8 == 0 and
+                    d[s] <= 64 and R >= self.dbits_min_res and
+                    f(B=B, H=R, W=R, cin=d[s], cout=d[s], flags=L.CONV_MASK | L.CONV_AUX_BITS))
 
+    @_memo
     def _rgbw(self):
         """Whether the final backward pass computes the top fromRGB weight / bias gradients in
         the epilogue of the top conv a's input gradient (PG_CONV_RGBW: that gradient, which only
         the fromRGB weight gradient reads in this pass, is never written)."""
-        key = ("rgbw", 0, 0, 0, 0)
-        if key not in self._ws_cache:
-            f = self._conv_sup()
-            d, s, R, B = self.depths, self.s, self.R, self.B
-            ok = bool(self.fuse_rgbw and self._rgbbits() and hasattr(self.ops, "conv3x3_rgbw") and
-                      f(B=B, H=R, W=R, cin=d[s], cout=d[s],
-                        flags=L.CONV_MASK | L.CONV_AUX_BITS | L.CONV_RGBW))
-            self._ws_cache[key] = ok
-        return self._ws_cache[key]
+        f = self._conv_sup()
+        d, s, R, B = self.depths, self.s, self.R, self.B
+        return bool(self.fuse_rgbw and self._rgbbits() and hasattr(self.ops, "conv3x3_rgbw") and
+                    f(B=B, H=R, W=R, cin=d[s], cout=d[s],
+                      flags=L.CONV_MASK | L.CONV_AUX_BITS | L.CONV_RGBW))
 
+    @_memo
     def _rgbd(self):
         """Whether the input-gradient passes (the penalty's B1, the G half's) compute the top
         fromRGB input gradient, its squared norms and (R1) the tangent's fromRGB weight term in
         the epilogue of the top conv a's input gradient (PG_CONV_RGBD: that gradient is never
         written)."""
-        key = ("rgbd", 0, 0, 0, 0)
-        if key not in self._ws_cache:
-            f = self._conv_sup()
-            d, s, R, B = self.depths, self.s, self.R, self.B
-            ok = bool(self.fuse_rgbd and self._rgbbits() and hasattr(self.ops, "conv3x3_rgbd") and
-                      B <= 16 and
-                      f(B=B, H=R, W=R, cin=d[s], cout=d[s],
-                        flags=L.CONV_MASK | L.CONV_AUX_BITS | L.CONV_RGBD))
-            self._ws_cache[key] = ok
-        return self._ws_cache[key]
+        f = self._conv_sup()
+        d, s, R, B = self.depths, self.s, self.R, self.B
+        return bool(self.fuse_rgbd and self._rgbbits() and hasattr(self.ops, "conv3x3_rgbd") and
+                    B <= 16 and
+                    f(B=B, H=R, W=R, cin=d[s], cout=d[s],
+                      flags=L.CONV_MASK | L.CONV_AUX_BITS | L.CONV_RGBD))
 
+    @_memo
     def _pn_pool(self, i):
         """Whether level i's conv-a input gradient (pooled to level i-1) also applies level
         i-1's conv-b PixelNorm + LReLU backward (PG_CONV_POOL | PG_CONV_PNBWD): level i-1's
         forward kept y and r (fused PixelNorm) and the kernel supports it (32 channels)."""
-        key = ("pnpool", i, 0, 0, 0)
-        if key not in self._ws_cache:
-            f = getattr(self.ops, "conv_supported", None)
-            d, Ri, B = self.depths, 8 * 2 ** i, self.B
-            ok = bool(i >= 1 and f is not None and self.fuse_pn_pool and
-                      self._pn_fused(Ri // 2, d[i], d[i], L.CONV_LRELU) and
-                      f(B=B, H=Ri, W=Ri, cin=d[i + 1], cout=d[i],
-                        flags=L.CONV_POOL | L.CONV_PNBWD))
-            self._ws_cache[key] = ok
-        return self._ws_cache[key]
+        f = getattr(self.ops, "conv_supported", None)
+        d, Ri, B = self.depths, 8 * 2 ** i, self.B
+        return bool(i >= 1 and f is not None and self.fuse_pn_pool and
+                    self._pn_fused(Ri // 2, d[i], d[i], L.CONV_LRELU) and
+                    f(B=B, H=Ri, W=Ri, cin=d[i + 1], cout=d[i],
+                      flags=L.CONV_POOL | L.CONV_PNBWD))
 
+    @_memo
     def _pn_fused(self, H, cin, cout, flags):
         """Whether this generator conv can run PixelNorm in its epilogue (all output
         channels in one tile of the kernel the library picks for the shape)."""
-        key = ("pn", H, cin, cout, flags)
-        if key not in self._ws_cache:
-            f = getattr(self.ops, "conv_supported", None)
-            ok = bool(self.fuse_pixnorm and f is not None)
-            for b in self._GBs:   # the generator forward runs at B and, merged, at 2B
-                need = self._ws_need("c", H, cin, cout, False, b)
-                ok = ok and bool(f(B=b, H=H, W=H, cin=cin, cout=cout,
-                                   flags=flags | L.CONV_PIXNORM | L.CONV_BIAS, ws_bytes=need))
-            self._ws_cache[key] = ok
-        return self._ws_cache[key]
+        f = getattr(self.ops, "conv_supported", None)
+        ok = bool(self.fuse_pixnorm and f is not None)
+        for b in self._GBs:   # the generator forward runs at B and, merged, at 2B
+            need = self._ws_need("c", H, cin, cout, False, b)
+            ok = ok and bool(f(B=b, H=H, W=H, cin=cin, cout=cout,
+                               flags=flags | L.CONV_PIXNORM | L.CONV_BIAS, ws_bytes=need))
+        return ok
 
+    @_memo
     def _pnb_fused(self, H, cin, cout):
         """Whether conv a (cin -> cout, up2 input) of a generator block has its PixelNorm
         backward fused into the input-gradient conv of conv b (cout -> cout) that produces
         its upstream gradient: needs the fused forward (y and r stored) and a tile holding
         every channel."""
-        key = ("pnb", H, cin, cout)
-        if key not in self._ws_cache:
-            f = getattr(self.ops, "conv_supported", None)
-            ok = bool(self.fuse_pixnorm and self.fuse_pnbwd and f is not None and
-                      self._pn_fused(H, cin, cout, L.CONV_UPS_IN | L.CONV_LRELU))
-            if ok:
-                need = self._ws_need("c", H, cout, cout, False)
-                ok = bool(f(B=self.B, H=H, W=H, cin=cout, cout=cout, flags=L.CONV_PNBWD,
-                            ws_bytes=need))
-            self._ws_cache[key] = ok
-        return self._ws_cache[key]
+        f = getattr(self.ops, "conv_supported", None)
+        ok = bool(self.fuse_pixnorm and self.fuse_pnbwd and f is not None and
+                  self._pn_fused(H, cin, cout, L.CONV_UPS_IN | L.CONV_LRELU))
+        if ok:
+            need = self._ws_need("c", H, cout, cout, False)
+            ok = bool(f(B=self.B, H=H, W=H, cin=cout, cout=cout, flags=L.CONV_PNBWD,
+                        ws_bytes=need))
+        return ok
 
     def _g_conv_pn(self, key, x, u, y, r, H, cin, cout, flags, keep):
         """conv + lrelu + PixelNorm of a generator block (lib/blocks.py:126-139): fused
@@ -865,22 +842,21 @@ class StepEngine:
             self.trace("G", self)
         return g["img"]
 
+    @_memo
     def _rgbo(self):
         """Whether the top conv b can write the toRGB output in its epilogue (PG_CONV_RGBO): the
         fused PixelNorm forward on a tile holding every channel, at every batch the G forward
         runs (B, and 2B merged)."""
-        if "rgbo" not in self._ws_cache:
-            s, d = self.s, self.depths
-            f = getattr(self.ops, "conv_supported", None)
-            ok = bool(self.fuse_rgbo and self.fuse_pixnorm and f is not None and
-                      hasattr(self.ops, "conv3x3_rgbo") and
-                      self._pn_fused(self.R, d[s], d[s], L.CONV_LRELU))
-            if ok:
-                flags = L.CONV_PIXNORM | L.CONV_LRELU | L.CONV_BIAS | L.CONV_RGBO
-                ok = all(f(B=b, H=self.R, W=self.R, cin=d[s], cout=d[s], flags=flags, ws_bytes=0)
-                         for b in (self.B, 2 * self.B))
-            self._ws_cache["rgbo"] = ok
-        return self._ws_cache["rgbo"]
+        s, d = self.s, self.depths
+        f = getattr(self.ops, "conv_supported", None)
+        ok = bool(self.fuse_rgbo and self.fuse_pixnorm and f is not None and
+                  hasattr(self.ops, "conv3x3_rgbo") and
+                  self._pn_fused(self.R, d[s], d[s], L.CONV_LRELU))
+        if ok:
+            flags = L.CONV_PIXNORM | L.CONV_LRELU | L.CONV_BIAS | L.CONV_RGBO
+            ok = all(f(B=b, H=self.R, W=self.R, cin=d[s], cout=d[s], flags=flags, ws_bytes=0)
+                     for b in (self.B, 2 * self.B))
+        return ok
 
     def _ylvl(self, j):
         return self.g["y0"] if j == 0 else self.g[f"yb{j - 1}"]
@@ -892,6 +868,12 @@ class StepEngine:
     def _top_out(self, alpha):
         """D's output of the top block after the fade-in blend."""
         return self.dd["hblend"] if self._low(alpha) else self.dd[f"p{self.s - 1}"]
+
+    def _mbstd_in(self, low):
+        """The minibatch-stddev input (D's level-0 output) in the current buffer set, whose
+        key depends on the stage and the fade-in only: every pass looks it up in the set it
+        runs on (the merged set's activations are the batch-B sets' at 2B)."""
+        return self.dd["yrgb" if self.s == 0 else "hblend" if (self.s == 1 and low) else "p0"]
 
     def _rgb_out(self, P, alpha):
         s, d, g = self.s, self.depths, self.g
@@ -1019,26 +1001,19 @@ class StepEngine:
         for i in reversed(range(s)):                                           # :260-265
             Ri = 8 * 2 ** i
             self._conv("D", f"a{i}", h, D[f"a{i}"], Ri, d[i + 1], d[i + 1], L.CONV_LRELU)
-            if self._dbits(i):
-                self._conv("D", f"b{i}", D[f"a{i}"], D[f"p{i}"], Ri, d[i + 1], d[i],
-                           L.CONV_LRELU | L.CONV_POOL | L.CONV_Y2_BITS, y2=D[f"mb{i}"],
-                           out_scale=0.25)
-            elif self._ubits(i):
-                self._conv("D", f"b{i}", D[f"a{i}"], D[f"p{i}"], Ri, d[i + 1], d[i],
-                           L.CONV_LRELU | L.CONV_POOL | L.CONV_Y2_BITS, y2=D[f"mb{i}"],
-                           out_scale=0.25)
-            else:
+            if self._dmode(i) == "act":
                 self._conv("D", f"b{i}", D[f"a{i}"], D[f"p{i}"], Ri, d[i + 1], d[i],
                            L.CONV_LRELU | L.CONV_POOL, y2=D[f"bf{i}"], out_scale=0.25)
+            else:   # "bits" / "ubits": the pre-pool sign as bits
+                self._conv("D", f"b{i}", D[f"a{i}"], D[f"p{i}"], Ri, d[i + 1], d[i],
+                           L.CONV_LRELU | L.CONV_POOL | L.CONV_Y2_BITS, y2=D[f"mb{i}"],
+                           out_scale=0.25)
             if i == s - 1 and low:
                 ops.blend(1.0 - alpha, D["yd"], alpha, D[f"p{i}"], D["hblend"])
                 h = D["hblend"]
             else:
                 h = D[f"p{i}"]
-        self.h_mb = h
-        # the D-buffer key of the mbstd input (the merged second backward needs its 2B view)
-        self.h_mb_key = "yrgb" if s == 0 else ("hblend" if (s == 1 and low) else "p0")
-        ops.mbstd_fwd(h, D["m"], B=B, HW=16, C=d[0])                           # blocks.py:261
+        ops.mbstd_fwd(h, D["m"], B=B, HW=16, C=d[0])     # blocks.py:261; h is _mbstd_in(low)
         self._conv("D", "mb", D["m"], D["c"], 4, d[0] + 1, d[0], L.CONV_LRELU)
         mb = "minibatch_normalization_block.linear.module."
         ops.linear(D["c"], P[mb + "weight"], P[mb + "bias"], D["l1"], B=B,
@@ -1075,24 +1050,57 @@ class StepEngine:
         final: the last pass writing D's gradients this half-step (grad_ready calls); its top
         level's conv-a and fromRGB weight gradients run on the main stream (_tail_main).
         join=False: the pass writes buffers no pending side-stream launch reads (the merged
-        second backward's own set, dd2b)."""
-        ops, D, d, s, B, R = self.ops, self.dd, self.depths, self.s, self.B, self.R
+        second backward's own set, dd2b).
+        t_dw: the fromRGB weight gradient the R1 tangent pass adds its term to; returns whether
+        this pass added that term already (d_tangent's rgb_done)."""
+        ops, D, d, s, B = self.ops, self.dd, self.depths, self.s, self.B
         if join:
             self._side_join("D")
-        # the side-stream point after every weight term issued so far (the tangent's): a
-        # main-stream weight gradient accumulating onto one of them waits for it
-        self._tail_ev = self._side_ev.get("D")
+        low = self._low(alpha)
         tail = final and GR is not None and self._tail_main_on()
-        fr = "fromRGB_blocks.{}.fromRGB.module."
-        rgbw = (tail and gimg is None and s >= 1 and isinstance(img, torch.Tensor) and
-                self._rgbw())
-        # the input-gradient passes: gimg (+ norms, + the R1 tangent's fromRGB weight term
-        # t_dw, s / B) from the top conv a's epilogue (t_dw only without the fade-in branch,
-        # whose gradient joins gimg afterwards)
-        rgbd = (GR is None and gimg is not None and gimg_overwrite and s >= 1 and self._rgbd())
-        low_a = self._low(alpha)
-        self._t_rgb_done = bool(rgbd and t_dw is not None and not low_a)
+        # the top conv a's input gradient, which only the fromRGB layer's backward reads:
+        #   "rgbw"   the final pass: the fromRGB weight gradient from the conv's epilogue;
+        #   "rgbd"   the input-gradient passes: gimg (+ norms, + the R1 tangent's fromRGB weight
+        #            term t_dw, s / B) from the epilogue;
+        #   "store"  written to gzrgb for the separate fromRGB launches
+        if tail and gimg is None and s >= 1 and isinstance(img, torch.Tensor) and self._rgbw():
+            top = "rgbw"
+        elif GR is None and gimg is not None and gimg_overwrite and s >= 1 and self._rgbd():
+            top = "rgbd"
+        else:
+            top = "store"
+        # t_dw only without the fade-in branch, whose gradient joins gimg afterwards
+        t_rgb_done = top == "rgbd" and t_dw is not None and not low
         ready = (lambda *p: self._ready("D", *p)) if final else (lambda *p: None)
+        # the side-stream point after every weight term issued so far (the tangent's): the
+        # pass's first main-stream weight gradient, accumulating onto them, waits for it
+        tail_ev = self._side_ev.get("D")
+
+        def tail_wait():
+            nonlocal tail_ev
+            ev, tail_ev = tail_ev, None
+            if ev is not None:
+                cur = torch.cuda.current_stream()
+                if isinstance(ev, torch.cuda.Event):
+                    cur.wait_event(ev)
+                else:
+                    ev.wait(cur)
+
+        tail_jobs = []   # (order, _wgrad args, kwargs, grad_ready prefix) run at the tail
+
+        def wgrad(c, i, x, gz, pre, cin, cout, in_tail, **kw):
+            """The weight gradient of level i's conv c ("a" / "b"): none in an input-gradient
+            pass, deferred to the main-stream tail, or now on the side stream."""
+            if GR is None:
+                return
+            args = (f"{c}{i}", x, gz, GR[pre + "weight"], 8 * 2 ** i, cin, cout)
+            kw["db"] = GR[pre + "bias"]
+            if in_tail:
+                tail_jobs.append(((-i, c), args, kw, pre))
+            else:
+                self._wgrad("D", *args, **kw)
+                ready(pre)
+
         dec = "decision_layer.module."
         lin = "minibatch_normalization_block.linear.module."
         if GR is not None:
@@ -1116,12 +1124,10 @@ class StepEngine:
                         db=GR[cv + "bias"])
             ready(cv)
         self._conv("D", "mb", D["gzc"], D["gm"], 4, d[0], r4(d[0] + 1), 0, dgrad=True)
-        ops.mbstd_bwd(self.h_mb, D["gm"], D["gh"], B=B, HW=16, C=d[0])
+        ops.mbstd_bwd(self._mbstd_in(low), D["gm"], D["gh"], B=B, HW=16, C=d[0])
         if inj_mbstd is not None:
             ops.blend(1.0, D["gh"], 1.0, inj_mbstd, D["gh"])
         g = D["gh"]
-        low = self._low(alpha)
-        tail_jobs = []   # (order, _wgrad args, kwargs, grad_ready prefix) run at the tail
         for i in range(s):
             Ri = 8 * 2 ** i
             a, b = f"blocks.{i}.block.0.module.", f"blocks.{i}.block.2.module."
@@ -1135,111 +1141,101 @@ class StepEngine:
             # is the step's critical path at this point
             in_tail = tail and i >= s - max(1, self.tail_levels)
             tail_b = in_tail and (i < s - 1 or self.tail_b)
-            if self._dbits(i):
+            mode = self._dmode(i)
+            if mode == "bits":
                 # gzb = sc * up2(g) * lrelu'(bits): read by the kernels from g and the bits
-                wgb = dict(db=GR[b + "bias"], gzbits=D[f"mb{i}"], gscale=sc) if GR is not None else None
-                if GR is not None and not tail_b:
-                    self._wgrad("D", f"b{i}", D[f"a{i}"], g, GR[b + "weight"], Ri, d[i + 1], d[i],
-                                **wgb)
-                    ready(b)
-                elif tail_b:
-                    tail_jobs.append(((-i, 1), (f"b{i}", D[f"a{i}"], g, GR[b + "weight"], Ri,
-                                                d[i + 1], d[i]), wgb, b))
+                wgrad("b", i, D[f"a{i}"], g, b, d[i + 1], d[i], tail_b, gzbits=D[f"mb{i}"],
+                      gscale=sc)
                 self._conv("D", f"b{i}", g, D[f"gza{i}"], Ri, d[i], d[i + 1],
                            L.CONV_MASK | L.CONV_UPS_IN | L.CONV_X_BITS, aux=D[f"a{i}"],
                            dgrad=True, out_scale=sc, xbits=D[f"mb{i}"])
             else:
-                if self._ubits(i):
+                if mode == "ubits":
                     ops.unpool_mask(g, None, D[f"gzb{i}"], B=B, H=Ri, W=Ri, C=d[i], scale=sc,
                                     slope=SLOPE, ups=True, bits=D[f"mb{i}"])
                 else:
                     ops.unpool_mask(g, D[f"bf{i}"], D[f"gzb{i}"], B=B, H=Ri, W=Ri, C=d[i], scale=sc,
                                     slope=SLOPE, ups=True)
-                wgb = dict(db=GR[b + "bias"]) if GR is not None else None
-                if GR is not None and not tail_b:
-                    self._wgrad("D", f"b{i}", D[f"a{i}"], D[f"gzb{i}"], GR[b + "weight"], Ri,
-                                d[i + 1], d[i], **wgb)
-                    ready(b)
-                elif tail_b:
-                    tail_jobs.append(((-i, 1), (f"b{i}", D[f"a{i}"], D[f"gzb{i}"], GR[b + "weight"],
-                                                Ri, d[i + 1], d[i]), wgb, b))
+                wgrad("b", i, D[f"a{i}"], D[f"gzb{i}"], b, d[i + 1], d[i], tail_b)
                 self._conv("D", f"b{i}", D[f"gzb{i}"], D[f"gza{i}"], Ri, d[i], d[i + 1],
                            L.CONV_MASK, aux=D[f"a{i}"], dgrad=True)
             hin = D["yrgb"] if i == s - 1 else (self._top_out(alpha) if i == s - 2 else D[f"p{i + 1}"])
-            top_tail = tail and i == s - 1
-            if GR is not None and not in_tail:
-                self._wgrad("D", f"a{i}", hin, D[f"gza{i}"], GR[a + "weight"], Ri, d[i + 1],
-                            d[i + 1],
-                            db=GR[a + "bias"])
-                ready(a)
-            elif in_tail:
-                tail_jobs.append(((-i, 0), (f"a{i}", hin, D[f"gza{i}"], GR[a + "weight"], Ri,
-                                            d[i + 1], d[i + 1]), dict(db=GR[a + "bias"]), a))
-            if i == s - 1 and rgbd:
-                fw = fr.format(s) + "weight"
-                ops.conv3x3_rgbd(D[f"gza{i}"], self.packs[("D", f"a{i}")][1], B=B, H=Ri, W=Ri,
-                                 cin=d[i + 1], cout=d[i + 1], flags=L.CONV_MASK | L.CONV_AUX_BITS,
-                                 slope=SLOPE, aux=D["rgbb"], w_rgb=P[fw], f=he(3), gimg=gimg,
-                                 norms=None if low_a else norms,
-                                 dw=t_dw if self._t_rgb_done else None, s=he(3) / B)
-            elif i == s - 1 and rgbw:
-                # the fromRGB weight gradient in this conv's epilogue: its result is not stored
-                self._tail_wait()   # after the tangent's fromRGB weight term (side stream)
-                fw = fr.format(s)
-                ops.conv3x3_rgbw(D[f"gza{i}"], self.packs[("D", f"a{i}")][1], B=B, H=Ri, W=Ri,
-                                 cin=d[i + 1], cout=d[i + 1], flags=L.CONV_MASK | L.CONV_AUX_BITS,
-                                 slope=SLOPE, aux=D["rgbb"], img=img, s=he(3),
-                                 dw=GR[fw + "weight"], db=GR[fw + "bias"])
-            elif i == s - 1 and self._rgbbits():
-                self._conv("D", f"a{i}", D[f"gza{i}"], D["gzrgb"], Ri, d[i + 1], d[i + 1],
-                           L.CONV_MASK | L.CONV_AUX_BITS, aux=D["rgbb"], dgrad=True)
-            elif i == s - 1:
-                self._conv("D", f"a{i}", D[f"gza{i}"], D["gzrgb"], Ri, d[i + 1], d[i + 1],
-                           L.CONV_MASK, aux=D["yrgb"], dgrad=True)
-            else:
+            wgrad("a", i, hin, D[f"gza{i}"], a, d[i + 1], d[i + 1], in_tail)
+            if i < s - 1:
                 self._conv("D", f"a{i}", D[f"gza{i}"], D[f"ghin{i}"], Ri, d[i + 1], d[i + 1], 0,
                            dgrad=True)
                 g = D[f"ghin{i}"]
-            if top_tail:
-                # the input-gradient chain ends here: the deferred weight gradients on the main
-                # stream (idle otherwise) while the side stream drains its queue, the top
-                # level's first, conv a before conv b
-                self._tail_wait()
-                for _, args, kw, pre in sorted(tail_jobs, key=lambda j: j[0]):
-                    self._wgrad("D", *args, main=True, **kw)
-                    self._ready_main("D", pre)
+
+        self._d_backward_top(P, GR, low, top, tail, tail_wait, tail_jobs, ready, img=img,
+                             gimg=gimg, gimg_overwrite=gimg_overwrite, norms=norms,
+                             t_dw=t_dw if t_rgb_done else None)
+        return t_rgb_done
+
+    def _d_backward_top(self, P, GR, low, top, tail, tail_wait, tail_jobs, ready, *, img, gimg,
+                        gimg_overwrite, norms, t_dw):
+        """The fromRGB end of d_backward, on both streams in this order: the top conv a's input
+        gradient in the treatment `top` (s = 0: the mbstd input's lrelu backward instead), the
+        weight gradients deferred to the main-stream tail, the top fromRGB layer's weight and
+        input gradients where no epilogue took them, and the fade-in's low-resolution branch."""
+        ops, D, d, s, B, R = self.ops, self.dd, self.depths, self.s, self.B, self.R
+        pre = f"fromRGB_blocks.{s}.fromRGB.module."
+        w, C = P[pre + "weight"], d[s]
         if s == 0:
             ops.unpool_mask(D["gh"], D["yrgb"], D["gzrgb"], B=B, H=4, W=4, C=d[0], scale=1.0,
                             slope=SLOPE, ups=False)
-        fr = "fromRGB_blocks.{}.fromRGB.module."
-        w = P[fr.format(s) + "weight"]
-        if rgbw:
-            self._ready_main("D", fr.format(s))
-        elif GR is not None and tail and gimg is None:
-            self._tail_wait()
-            ops.from_rgb_bwd(D["gzrgb"], w, he(3), B=B, R=R, C=d[s], down=False, img=img,
-                             dw=GR[fr.format(s) + "weight"], db=GR[fr.format(s) + "bias"])
-            self._ready_main("D", fr.format(s))
+        elif top == "store":
+            if self._rgbbits():
+                self._conv("D", f"a{s - 1}", D[f"gza{s - 1}"], D["gzrgb"], R, C, C,
+                           L.CONV_MASK | L.CONV_AUX_BITS, aux=D["rgbb"], dgrad=True)
+            else:
+                self._conv("D", f"a{s - 1}", D[f"gza{s - 1}"], D["gzrgb"], R, C, C, L.CONV_MASK,
+                           aux=D["yrgb"], dgrad=True)
+        else:
+            # the fromRGB backward in this conv's epilogue: its result is not stored
+            conv = dict(B=B, H=R, W=R, cin=C, cout=C, flags=L.CONV_MASK | L.CONV_AUX_BITS,
+                        slope=SLOPE, aux=D["rgbb"])
+            gza, wpk = D[f"gza{s - 1}"], self.packs[("D", f"a{s - 1}")][1]
+            if top == "rgbd":
+                ops.conv3x3_rgbd(gza, wpk, w_rgb=w, f=he(3), gimg=gimg,
+                                 norms=None if low else norms, dw=t_dw, s=he(3) / B, **conv)
+            else:
+                tail_wait()   # after the tangent's fromRGB weight term (side stream)
+                ops.conv3x3_rgbw(gza, wpk, img=img, s=he(3), dw=GR[pre + "weight"],
+                                 db=GR[pre + "bias"], **conv)
+        if tail and s >= 1:
+            # the input-gradient chain ends here: the deferred weight gradients on the main
+            # stream (idle otherwise) while the side stream drains its queue, the top
+            # level's first, conv a before conv b
+            tail_wait()
+            for _, args, kw, p in sorted(tail_jobs, key=lambda j: j[0]):
+                self._wgrad("D", *args, main=True, **kw)
+                self._ready_main("D", p)
+        if top == "rgbw":
+            self._ready_main("D", pre)
         elif GR is not None:
-            # img may be the generator's output buffer (fake pass): pending for both nets
-            self._side_call(("D", "G"), ops.from_rgb_bwd,
-                            D["gzrgb"], w, he(3), B=B, R=R, C=d[s], down=False, img=img,
-                            dw=GR[fr.format(s) + "weight"], db=GR[fr.format(s) + "bias"])
-            ready(fr.format(s))
-        if gimg is not None and not rgbd:
-            ops.from_rgb_bwd(D["gzrgb"], w, he(3), B=B, R=R, C=d[s], down=False, gimg=gimg,
+            wg = dict(B=B, R=R, C=C, down=False, img=img, dw=GR[pre + "weight"],
+                      db=GR[pre + "bias"])
+            if tail and gimg is None:
+                tail_wait()
+                ops.from_rgb_bwd(D["gzrgb"], w, he(3), **wg)
+                self._ready_main("D", pre)
+            else:
+                # img may be the generator's output buffer (fake pass): pending for both nets
+                self._side_call(("D", "G"), ops.from_rgb_bwd, D["gzrgb"], w, he(3), **wg)
+                ready(pre)
+        if gimg is not None and top != "rgbd":
+            ops.from_rgb_bwd(D["gzrgb"], w, he(3), B=B, R=R, C=C, down=False, gimg=gimg,
                              **self._gimg_kw(gimg_overwrite, None if low else norms))
         if low:
-            w1 = P[fr.format(s - 1) + "weight"]
+            pre = f"fromRGB_blocks.{s - 1}.fromRGB.module."
+            lo = dict(B=B, R=R // 2, C=d[s - 1], down=True)
             if GR is not None:
-                self._side_call(("D", "G"), ops.from_rgb_bwd,
-                                D["gzd"], w1, he(3), B=B, R=R // 2, C=d[s - 1], down=True, img=img,
-                                dw=GR[fr.format(s - 1) + "weight"],
-                                db=GR[fr.format(s - 1) + "bias"])
-                ready(fr.format(s - 1))
+                self._side_call(("D", "G"), ops.from_rgb_bwd, D["gzd"], P[pre + "weight"], he(3),
+                                img=img, dw=GR[pre + "weight"], db=GR[pre + "bias"], **lo)
+                ready(pre)
             if gimg is not None:
-                ops.from_rgb_bwd(D["gzd"], w1, he(3), B=B, R=R // 2, C=d[s - 1], down=True,
-                                 gimg=gimg, **self._gimg_kw(False, norms))
+                ops.from_rgb_bwd(D["gzd"], P[pre + "weight"], he(3), gimg=gimg,
+                                 **self._gimg_kw(False, norms), **lo)
 
     @staticmethod
     def _gimg_kw(overwrite, norms):
@@ -1250,46 +1246,35 @@ class StepEngine:
             kw["norms"] = norms
         return kw
 
-    def _fused_penalty(self):
-        """The penalties' squared norms fused into the input-gradient pass and their weighted
-        gradient read by the tangent pass through an image mix (the ops support it)."""
-        return hasattr(self.ops, "penalty_scale")
-
     def _input_grad(self, P, u, alpha, mode, w=0.0, GR=None):
-        """B1 of a penalty: dD/dx into D["gimg"] from the upstream u, the penalty into
-        loss[2] and the tangent pass's input gbar (R1: g / B; WGAN-GP: the weighted g).
+        """B1 of a penalty: dD/dx into D["gimg"] from the upstream u with its per-sample
+        squared norms summed by the same pass, the penalty into loss[2]; returns the tangent
+        pass's input gbar (R1: g / B; WGAN-GP: the weighted g) as an image mix, the scale
+        applied on load (lib/loss.py:125-135), and d_tangent's rgb_done.
         GR (R1): the D gradients, so the tangent's fromRGB weight term can be taken in this
         pass (PG_CONV_RGBD; d_tangent then skips it)."""
-        ops, D, B = self.ops, self.dd, self.B
-        if self._fused_penalty():
-            fw = f"fromRGB_blocks.{self.s}.fromRGB.module.weight"
-            self.d_backward(P, None, u, alpha, gimg=D["gimg"], gimg_overwrite=True,
-                            norms=D["gp_norms"],
-                            t_dw=GR[fw] if (GR is not None and mode == "r1") else None)
-            ops.penalty_scale(mode, D["gp_norms"], w, self.loss[2:3], D["gp_scale"])
-            return L.ImgMix(D["gimg"], a=D["gp_scale"])
-        D["gimg"].zero_()
-        self.d_backward(P, None, u, alpha, gimg=D["gimg"])
-        if mode == "r1":
-            ops.r1_penalty(D["gimg"], B, self.loss[2:3], D["gbar"])   # lib/loss.py:125-135
-        else:
-            ops.gp_penalty(D["gimg"], w, self.loss[2:3], D["gp_norms"], D["gbar"])
-        return D["gbar"]
+        D = self.dd
+        fw = f"fromRGB_blocks.{self.s}.fromRGB.module.weight"
+        rgb_done = self.d_backward(P, None, u, alpha, gimg=D["gimg"], gimg_overwrite=True,
+                                   norms=D["gp_norms"],
+                                   t_dw=GR[fw] if (GR is not None and mode == "r1") else None)
+        self.ops.penalty_scale(mode, D["gp_norms"], w, self.loss[2:3], D["gp_scale"])
+        return L.ImgMix(D["gimg"], a=D["gp_scale"]), rgb_done
 
-    def d_tangent(self, P, GR, gbar, u, alpha):
+    def d_tangent(self, P, GR, gbar, u, alpha, rgb_done=False):
         """Push gbar (= dR1/dx-gradient) forward through D with the B1 masks, adding the R1
-        weight terms; returns (tangent logit, mbstd injection) for the B2 pass."""
+        weight terms; returns (tangent logit, mbstd injection) for the B2 pass.
+        rgb_done: B1 added the top fromRGB weight term already (d_backward's result)."""
         ops, D, d, s, B, R = self.ops, self.dd, self.depths, self.s, self.B, self.R
         self._side_join("D")
         fr = "fromRGB_blocks.{}.fromRGB.module."
         mk = dict(mask_bits=D["rgbb"]) if self._rgbbits() else dict(mask_y=D["yrgb"])
         ops.from_rgb(gbar, P[fr.format(s) + "weight"], None, he(3), D["trgb"], B=B, R=R, C=d[s],
                      down=False, slope=SLOPE, **mk)
-        if not getattr(self, "_t_rgb_done", False):   # else B1's RGBD epilogue added it
+        if not rgb_done:
             self._side_call(("D",), ops.from_rgb_bwd,
                             D["gzrgb"], P[fr.format(s) + "weight"], he(3), B=B, R=R, C=d[s],
                             down=False, img=gbar, dw=GR[fr.format(s) + "weight"])
-        self._t_rgb_done = False
         low = self._low(alpha)
         if low:
             ops.from_rgb(gbar, P[fr.format(s - 1) + "weight"], None, he(3), D["td"], B=B, R=R // 2,
@@ -1304,34 +1289,31 @@ class StepEngine:
             self._conv("D", f"a{i}", t, D[f"ta{i}"], Ri, d[i + 1], d[i + 1], L.CONV_MASK,
                        aux=D[f"a{i}"], bias=False)
             self._wgrad("D", f"a{i}", t, D[f"gza{i}"], GR[a + "weight"], Ri, d[i + 1], d[i + 1])
-            if self._dbits(i):
-                # tangent through conv b, lrelu' (bits) and the avg pool in one launch; the
-                # weight term pairs the tangent with B1's gradient at this level
+            mode = self._dmode(i)
+            if mode == "act":
+                self._conv("D", f"b{i}", D[f"ta{i}"], D[f"tbf{i}"], Ri, d[i + 1], d[i],
+                           L.CONV_MASK, aux=D[f"bf{i}"], bias=False)
+            else:
+                # tangent through conv b, lrelu' (bits) and the avg pool in one launch
                 self._conv("D", f"b{i}", D[f"ta{i}"], D[f"tp{i}"], Ri, d[i + 1], d[i],
                            L.CONV_MASK | L.CONV_AUX_BITS | L.CONV_POOL, aux=D[f"mb{i}"],
                            bias=False, out_scale=0.25)
+            # the weight term pairs the tangent with B1's gradient at conv b's output
+            if mode == "bits":   # never materialised: the pooled-resolution gradient and the bits
                 gb1 = D["gh"] if i == 0 else D[f"ghin{i - 1}"]
                 self._wgrad("D", f"b{i}", D[f"ta{i}"], gb1, GR[b + "weight"], Ri, d[i + 1], d[i],
                             gzbits=D[f"mb{i}"], gscale=0.25 * (alpha if i == s - 1 else 1.0))
-            elif self._ubits(i):
-                # mask (bits) and pool in the conv; the weight term reads B1's materialised gzb
-                self._conv("D", f"b{i}", D[f"ta{i}"], D[f"tp{i}"], Ri, d[i + 1], d[i],
-                           L.CONV_MASK | L.CONV_AUX_BITS | L.CONV_POOL, aux=D[f"mb{i}"],
-                           bias=False, out_scale=0.25)
-                self._wgrad("D", f"b{i}", D[f"ta{i}"], D[f"gzb{i}"], GR[b + "weight"], Ri,
-                            d[i + 1], d[i])
             else:
-                self._conv("D", f"b{i}", D[f"ta{i}"], D[f"tbf{i}"], Ri, d[i + 1], d[i],
-                           L.CONV_MASK, aux=D[f"bf{i}"], bias=False)
                 self._wgrad("D", f"b{i}", D[f"ta{i}"], D[f"gzb{i}"], GR[b + "weight"], Ri,
                             d[i + 1], d[i])
+            if mode == "act":
                 ops.avgpool2(D[f"tbf{i}"], D[f"tp{i}"], B=B, H=Ri, W=Ri, C=d[i])
             if i == s - 1 and low:
                 ops.blend(1.0 - alpha, D["td"], alpha, D[f"tp{i}"], D["tblend"])
                 t = D["tblend"]
             else:
                 t = D[f"tp{i}"]
-        ops.mbstd_r1(self.h_mb, t, D["gm"], D["tm"], D["inj"], B=B, HW=16, C=d[0])
+        ops.mbstd_r1(self._mbstd_in(low), t, D["gm"], D["tm"], D["inj"], B=B, HW=16, C=d[0])
         cv = "minibatch_normalization_block.conv.module."
         self._conv("D", "mb", D["tm"], D["tc"], 4, d[0] + 1, d[0], L.CONV_MASK, aux=D["c"],
                    bias=False)
@@ -1369,8 +1351,8 @@ class StepEngine:
             # ---- real: F, B1, R1, T, B2
             self.d_forward(PD, xr, alpha_D)
             ops.bce(D["logit"], True, 1.0, self.loss[0:1], D["u"], D["hl"])   # lib/loss.py:119-123
-            gbar = self._input_grad(PD, D["u"], alpha_D, "r1", GR=GD)          # lib/loss.py:125-135
-            tout, inj = self.d_tangent(PD, GD, gbar, D["u"], alpha_D)
+            gbar, rgb_done = self._input_grad(PD, D["u"], alpha_D, "r1", GR=GD)
+            tout, inj = self.d_tangent(PD, GD, gbar, D["u"], alpha_D, rgb_done)
             ops.mul_add(D["u"], tout.view(-1), D["hl"], D["u2"])
             self.d_backward(PD, GD, D["u2"], alpha_D, img=xr, inj_mbstd=inj)
         else:
@@ -1446,9 +1428,7 @@ class StepEngine:
                 self.d_forward(PD, X, alpha_D)                                  # :216, :228
         finally:
             self.trace = trace
-        h2 = self.h_mb
-        self.h_mb = h2[:B]
-        if trace is not None:   # one record per image, in the separate schedule's order
+        if trace is not None:  # one record per image, in the separate schedule's order
             trace("D", self)
             self.dd = self.dd_hi
             try:
@@ -1462,28 +1442,20 @@ class StepEngine:
             if hp.W_drift:
                 ops.drift(D1["logit"], hp.W_drift, self.loss[4:5], D1["u"])   # pggan/loss.py:94-100
             ops.bce(D2["logit"][B:], False, 1.0, self.loss[1:2], D2["u"][B:], None)
-            self.h_mb = h2
-            try:
-                with self._pair(b2=True):
-                    self.d_backward(PD, GD, D2["u"], alpha_D, img=X)
-            finally:
-                self.h_mb = h2[:B]
+            with self._pair(b2=True):
+                self.d_backward(PD, GD, D2["u"], alpha_D, img=X)
             self._wgan_gp(PD, GD, X[:B], X[B:], gp_eps, alpha_D)
             self._side_join()
             return X[:B], (img_fake.clone() if self.keep_fake_D else img_fake)
         ops.bce(D1["logit"], True, 1.0, self.loss[0:1], D1["u"], D1["hl"])    # lib/loss.py:119-123
         ops.bce(D2["logit"][B:], False, 1.0, self.loss[1:2], D2["u2"][B:], None)
-        gbar = self._input_grad(PD, D1["u"], alpha_D, "r1", GR=GD)              # lib/loss.py:125-135
-        tout, inj = self.d_tangent(PD, GD, gbar, D1["u"], alpha_D)
+        gbar, rgb_done = self._input_grad(PD, D1["u"], alpha_D, "r1", GR=GD)
+        tout, inj = self.d_tangent(PD, GD, gbar, D1["u"], alpha_D, rgb_done)
         ops.mul_add(D1["u"], tout.view(-1), D1["hl"], D1["u2"])
-        self.h_mb = h2
-        try:
-            with self._pair(b2=True):
-                # D2["inj"]: the tangent wrote the real half; the fake half stays zero
-                self.d_backward(PD, GD, D2["u2"], alpha_D, img=X, inj_mbstd=D2["inj"], final=True,
-                                join=not self.sep_b2)
-        finally:
-            self.h_mb = h2[:B]
+        with self._pair(b2=True):
+            # D2["inj"]: the tangent wrote the real half; the fake half stays zero
+            self.d_backward(PD, GD, D2["u2"], alpha_D, img=X, inj_mbstd=D2["inj"], final=True,
+                            join=not self.sep_b2)
         self._side_join()
         return X[:B], (img_fake.clone() if self.keep_fake_D else img_fake)
 
@@ -1536,8 +1508,8 @@ class StepEngine:
             self._copy(X[:B], real)
         self.d_forward(PD, X[:B], alpha_D)                                       # :216
         ops.bce(D1["logit"], True, 1.0, self.loss[0:1], D1["u"], D1["hl"])    # lib/loss.py:119-123
-        gbar = self._input_grad(PD, D1["u"], alpha_D, "r1", GR=GD)              # lib/loss.py:125-135
-        tout, inj = self.d_tangent(PD, GD, gbar, D1["u"], alpha_D)
+        gbar, rgb_done = self._input_grad(PD, D1["u"], alpha_D, "r1", GR=GD)
+        tout, inj = self.d_tangent(PD, GD, gbar, D1["u"], alpha_D, rgb_done)
         ops.mul_add(D1["u"], tout.view(-1), D1["hl"], D1["u2"])
         if before_fake is not None:
             before_fake()
@@ -1550,34 +1522,27 @@ class StepEngine:
         finally:
             self.dd = D1
         ops.bce(D2["logit"][B:], False, 1.0, self.loss[1:2], D2["u2"][B:], None)
-        self.h_mb = D2[self.h_mb_key]
-        try:
-            with self._pair(b2=True):
-                # D2["inj"]: the tangent wrote the real half; the fake half stays zero
-                self.d_backward(PD, GD, D2["u2"], alpha_D, img=X, inj_mbstd=D2["inj"], final=True,
-                                join=not self.sep_b2)
-        finally:
-            self.h_mb = D1[self.h_mb_key]
+        with self._pair(b2=True):
+            # D2["inj"]: the tangent wrote the real half; the fake half stays zero
+            self.d_backward(PD, GD, D2["u2"], alpha_D, img=X, inj_mbstd=D2["inj"], final=True,
+                            join=not self.sep_b2)
         self._side_join()
         return X[:B], (img_fake.clone() if self.keep_fake_D else img_fake)
 
     def _wgan_gp(self, PD, GD, xr, xf, eps, alpha):
         """Optional WGAN-GP mode (pggan/loss.py:54-92): interp -> D -> per-sample grad norm.
-        Fused form: the interpolation eps x_r + (1 - eps) x_f is read by the fromRGB layers
-        from x_r, x_f and eps (never written), the per-sample squared norm is summed by the
-        pass writing dD/dx, and the tangent pass reads dD/dx with the per-sample weight
+        The interpolation eps x_r + (1 - eps) x_f is read by the fromRGB layers from x_r, x_f
+        and eps (never written), the per-sample squared norm is summed by the pass writing
+        dD/dx, and the tangent pass reads dD/dx with the per-sample weight
         2 W_gp (|g| - 1) / |g| applied on load."""
-        ops, D, B = self.ops, self.dd, self.B
+        D = self.dd
         D["gp_eps"].copy_(eps)
-        if self._fused_penalty():
-            torch.sub(D["ones"].view(-1, 1), D["gp_eps"], out=D["gp_c"])
-            interp = L.ImgMix(xr, xf, D["gp_eps"], D["gp_c"])
-        else:
-            ops.gp_interp(xr, xf, D["gp_eps"], D["interp"])
-            interp = D["interp"]
+        torch.sub(D["ones"].view(-1, 1), D["gp_eps"], out=D["gp_c"])
+        interp = L.ImgMix(xr, xf, D["gp_eps"], D["gp_c"])
         self.d_forward(PD, interp, alpha)
-        gbar = self._input_grad(PD, D["ones"], alpha, "wgan-gp", self.hyper.W_gp)  # d(sum D)/dx
-        tout, inj = self.d_tangent(PD, GD, gbar, D["ones"], alpha)
+        gbar, rgb_done = self._input_grad(PD, D["ones"], alpha, "wgan-gp",
+                                          self.hyper.W_gp)                    # d(sum D)/dx
+        tout, inj = self.d_tangent(PD, GD, gbar, D["ones"], alpha, rgb_done)
         # upstream of the second backward: no BCE here, so no logit injection
         self.d_backward(PD, GD, D["zeros"], alpha, img=interp, inj_mbstd=inj, final=True)
 
@@ -1605,11 +1570,7 @@ class StepEngine:
             before_d()
         self.d_forward(PD, img, alpha_D)
         ops.bce(D["logit"], True, hp.W_adv, self.loss[3:4], D["u"], None)   # pggan/loss.py:5-14
-        if self._fused_penalty():
-            self.d_backward(PD, None, D["u"], alpha_D, gimg=D["gimg"], gimg_overwrite=True)
-        else:
-            D["gimg"].zero_()
-            self.d_backward(PD, None, D["u"], alpha_D, gimg=D["gimg"])
+        self.d_backward(PD, None, D["u"], alpha_D, gimg=D["gimg"], gimg_overwrite=True)
         self.g_backward(PG, GG, D["gimg"], alpha_G)
         self._side_join()
         return img

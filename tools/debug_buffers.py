@@ -23,12 +23,10 @@ for name, ops, dev in (("gpu", _lib.HipOps(torch.float32), "cuda"), ("cpu", CpuO
     eng.d_forward(fpD.views, real, a)
     snaps["F"] = {k: v.detach().float().cpu().clone() for k, v in eng.dd.items()}
     ops.bce(eng.dd["logit"], True, 1.0, eng.loss[0:1], eng.dd["u"], eng.dd["hl"])
-    eng.dd["gimg"].zero_()
-    eng.d_backward(fpD.views, None, eng.dd["u"], a, gimg=eng.dd["gimg"])
-    snaps["B1"] = {k: v.detach().float().cpu().clone() for k, v in eng.dd.items()}
-    ops.r1_penalty(eng.dd["gimg"], B, eng.loss[2:3], eng.dd["gbar"])
     fpD.grad.zero_()
-    tout, inj = eng.d_tangent(fpD.views, fpD.gviews, eng.dd["gbar"], eng.dd["u"], a)
+    gbar, rgb_done = eng._input_grad(fpD.views, eng.dd["u"], a, "r1", GR=fpD.gviews)
+    snaps["B1"] = {k: v.detach().float().cpu().clone() for k, v in eng.dd.items()}
+    tout, inj = eng.d_tangent(fpD.views, fpD.gviews, gbar, eng.dd["u"], a, rgb_done)
     snaps["T"] = {k: v.detach().float().cpu().clone() for k, v in eng.dd.items()}
     snaps["Tgrad"] = {k: v.detach().float().cpu().clone() for k, v in fpD.gviews.items()}
     runs[name] = snaps
