@@ -426,6 +426,36 @@ size_t pg_augment_workspace_bytes(int B, int H, int W);
 int pg_augment_u8(int B, int H, int W, const void* src, const float* params, float* ws,
                   size_t ws_bytes, float* dst, void* stream);
 
+/* ---- sliced Wasserstein distance on Laplacian-pyramid patches (the PGGAN paper's validation
+ * metric; DESIGN.md "Validation: sliced Wasserstein distance").  All fp32; images NCHW
+ * [B][3][S][S], S a power of two.  `quantize` != 0 reads the image as 8-bit:
+ * q(x) = rint(clip(127.5 x + 127.5, 0, 255)), ties to even (for pyramid level 0).
+ * Gaussian pyramid step: filter with k (x) k, k = [1 4 6 4 1] / 16, mirror boundary without
+ * repeating the edge sample, keep every second sample from 0: x [B][3][H][W] -> y
+ * [B][3][H/2][W/2], H = W a power of two >= 32; x and y 16-byte aligned. */
+int pg_swd_pyr_down(int B, int H, int W, const float* x, int quantize, float* y, void* stream);
+/* desc [B*K][3][7][7]: the 7x7 patch of fine [B][3][S][S] around each centre pos [B*K][2] =
+ * (y, x) int32 (patches b*K .. b*K+K-1 from image b; centres in [3, S-3), the caller's duty),
+ * minus, if coarse != NULL ([B][3][S/2][S/2]), up(coarse) at those pixels: zero-insert to
+ * double size, filter with 4 k (x) k, same boundary (the Laplacian level, never materialised).
+ * quantize applies to fine.  S >= 16. */
+int pg_swd_descriptors(int B, int S, const float* fine, const float* coarse, int K, const int* pos,
+                       int quantize, float* desc, void* stream);
+/* mean3[c], rstd3[c] = per-channel mean and 1 / population standard deviation over the n * 49
+ * values of channel c of desc [n][3][49] (two passes: the mean, then the centred squares;
+ * fp32 partials per workgroup in `scratch`, combined in double). */
+int pg_swd_stats(size_t n, const float* desc, float* mean3, float* rstd3, void* scratch,
+                 void* stream);
+/* proj[p * proj_stride + i] = sum_j ((desc[i][j] - mean3[c(j)]) * rstd3[c(j)]) * dirs[j * P + p]
+ * for i < n, p < P, j < 147, c(j) = j / 49 (fp32 FMA); elements i >= n of a row are not
+ * written.  proj_stride >= n. */
+int pg_swd_project(size_t n, const float* desc, const float* mean3, const float* rstd3, int P,
+                   const float* dirs, float* proj, size_t proj_stride, void* stream);
+/* out[0] += sum over p < P, i < n of |a[p * stride + i] - b[p * stride + i]|, in a fixed order
+ * (fp32 partials per workgroup in `scratch`, combined in double).  P <= 65535. */
+int pg_swd_l1(int P, size_t n, const float* a, const float* b, size_t stride, float* out,
+              void* scratch, void* stream);
+
 /* ---- stream ordering between the engine's streams (weight gradients on a side stream).
  * torch's cross-stream events record with a system-scope release: every record writes back and
  * invalidates the L2 of all XCDs and the next kernel on that stream starts ~6.5 us late.  The

@@ -165,6 +165,11 @@ _SIGS = {
     "pg_cast": ([_I, _I, _SZ, _VP, _VP, _VP], _I),
     "pg_augment_workspace_bytes": ([_I, _I, _I], _SZ),
     "pg_augment_u8": ([_I, _I, _I, _VP, _VP, _VP, _SZ, _VP, _VP], _I),
+    "pg_swd_pyr_down": ([_I, _I, _I, _VP, _I, _VP, _VP], _I),
+    "pg_swd_descriptors": ([_I, _I, _VP, _VP, _I, _VP, _I, _VP, _VP], _I),
+    "pg_swd_stats": ([_SZ, _VP, _VP, _VP, _VP, _VP], _I),
+    "pg_swd_project": ([_SZ, _VP, _VP, _VP, _I, _VP, _VP, _SZ, _VP], _I),
+    "pg_swd_l1": ([_I, _SZ, _VP, _VP, _SZ, _VP, _VP, _VP], _I),
     "pg_step_plan_create": ([_I, _I, ctypes.POINTER(ctypes.c_int), _I, _I,
                              ctypes.POINTER(ctypes.c_void_p)], _I),
     "pg_step_plan_workspace_size": ([_VP], _SZ),
@@ -783,6 +788,53 @@ class HipOps:
         self._chk(self.lib.pg_augment_u8(B, H, W, _p(src), _p(params), _p(ws), ws.numel() * 4,
                                          _p(dst), self._s()), "augment_u8")
         return ws
+
+    # -- sliced Wasserstein distance (pggan_amd/metrics.py, csrc/swd.hip) ----
+    def _f32c(self, *ts):
+        self._cuda(*ts)
+        for t in ts:
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+                raise RuntimeError("pggan_amd: the swd ops take contiguous fp32 tensors")
+
+    def swd_pyr_down(self, x, y, quantize):
+        """x [B,3,S,S] -> y [B,3,S/2,S/2]: one Gaussian pyramid step (pg_swd_pyr_down)."""
+        self._f32c(x, y)
+        B, _, H, W = x.shape
+        self._chk(self.lib.pg_swd_pyr_down(B, H, W, _p(x), 1 if quantize else 0, _p(y), self._s()),
+                  "swd_pyr_down")
+
+    def swd_descriptors(self, fine, coarse, pos, desc, K, quantize):
+        """desc [B*K,147]: 7x7x3 patches of fine - up(coarse) (coarse None: of fine) at the
+        centres pos int32 [B*K,2] = (y, x), each in [3, S-3) (pg_swd_descriptors)."""
+        self._f32c(fine, coarse, desc)
+        self._cuda(pos)
+        B, S = fine.shape[0], fine.shape[-1]
+        assert pos.dtype == torch.int32 and pos.is_contiguous() and pos.numel() == 2 * B * K
+        assert desc.numel() == B * K * 147
+        self._chk(self.lib.pg_swd_descriptors(B, S, _p(fine), _p(coarse), K, _p(pos),
+                                              1 if quantize else 0, _p(desc), self._s()),
+                  "swd_descriptors")
+
+    def swd_stats(self, desc, mean3, rstd3):
+        """Per-channel mean and 1 / population std of desc [n,147] (pg_swd_stats)."""
+        self._f32c(desc, mean3, rstd3)
+        self._chk(self.lib.pg_swd_stats(desc.shape[0], _p(desc), _p(mean3), _p(rstd3), self._scr(),
+                                        self._s()), "swd_stats")
+
+    def swd_project(self, desc, mean3, rstd3, dirs, proj):
+        """proj [P, stride >= n] rows = normalised desc [n,147] @ dirs [147,P] (pg_swd_project)."""
+        self._f32c(desc, mean3, rstd3, dirs, proj)
+        assert dirs.shape[0] == 147 and proj.shape[0] == dirs.shape[1]
+        self._chk(self.lib.pg_swd_project(desc.shape[0], _p(desc), _p(mean3), _p(rstd3),
+                                          dirs.shape[1], _p(dirs), _p(proj), proj.shape[1],
+                                          self._s()), "swd_project")
+
+    def swd_l1(self, a, b, n, out):
+        """out[0] += sum |a - b| over the first n columns of the rows of a, b [P, stride]."""
+        self._f32c(a, b, out)
+        assert a.shape == b.shape
+        self._chk(self.lib.pg_swd_l1(a.shape[0], n, _p(a), _p(b), a.shape[1], _p(out), self._scr(),
+                                     self._s()), "swd_l1")
 
     def cast(self, x, y):
         self._cuda(x, y)

@@ -1,0 +1,140 @@
+"""Validation metric: the PGGAN paper's sliced Wasserstein distance (SWD) between two image
+sets, on 7x7x3 patches of the Laplacian pyramid (Karras et al. 2018, section 5 / appendix;
+DESIGN.md "Validation: sliced Wasserstein distance").
+
+The pyramid, the patch gather (with the Laplacian evaluated at the patch pixels only), the
+per-channel statistics, the projections and the sorted-L1 sum run in the library
+(csrc/swd.hip through the op set's swd_* methods).  The host side owns the bookkeeping and
+the random draws -- patch centres and directions, from seeded torch CPU generators -- and
+calls torch.sort for the sort.
+
+    m = SlicedWasserstein(ops, 256, 4096)
+    for batch in reals: m.feed("real", batch)      # fp32 [B, 3, 256, 256] in [-1, 1]
+    for batch in fakes: m.feed("fake", batch)
+    m.result()   # {256: v, 128: v, 64: v, 32: v, 16: v, "avg": v}, x 1e3 as the paper prints
+"""
+from __future__ import annotations
+
+import torch
+
+DESC = 147                   # 7 x 7 x 3 values per descriptor
+SETS = ("real", "fake")
+SORT_INDEX_BYTES = 1 << 30   # torch.sort also returns int64 indices: rows are sorted in chunks
+
+
+def _mix(*key):
+    """One 63-bit generator seed from a tuple of small non-negative integers."""
+    h = 0x9E3779B97F4A7C15
+    for k in key:
+        h = ((h ^ (int(k) + 0x632BE59BD9B4E019)) * 0xFF51AFD7ED558CCD) % (1 << 64)
+        h ^= h >> 32
+    return h >> 1
+
+
+def draw_positions(seed, level, first, count, size, per_image):
+    """Patch centres (y, x), uniform in [3, size - 3), of images first .. first + count - 1 of
+    a set at pyramid level `level`: int32 [count * per_image, 2].  Every image has its own
+    stream keyed by (seed, level, index of the image in its set), so how the images are
+    batched does not matter.  Image i of the reals and image i of the fakes get the same
+    centres (common random numbers: no bias, less variance, and two identical sets are at
+    distance exactly 0)."""
+    g = torch.Generator()
+    out = torch.empty(count, per_image, 2, dtype=torch.int32)
+    for i in range(count):
+        g.manual_seed(_mix(seed, 1, level, first + i))
+        out[i] = torch.randint(3, size - 3, (per_image, 2), generator=g, dtype=torch.int32)
+    return out.view(-1, 2)
+
+
+def draw_directions(seed, repeats, dirs):
+    """fp32 [repeats, 147, dirs]: N(0, 1) columns scaled to unit L2 norm, drawn and normalised
+    in float64."""
+    g = torch.Generator().manual_seed(_mix(seed, 2))
+    d = torch.randn(repeats, DESC, dirs, generator=g, dtype=torch.float64)
+    return (d / d.square().sum(dim=1, keepdim=True).sqrt()).float()
+
+
+class SlicedWasserstein:
+    """SWD x 1e3 per pyramid level (resolution .. 16) between `n_images` reals and as many
+    fakes.  Memory: two [n_images * per_image, 147] fp32 descriptor buffers per level
+    (1.2 GB each at the paper's 16384 images) and, in result(), two [dirs, n] projections."""
+
+    def __init__(self, ops, resolution, n_images, nhood=7, per_image=128, repeats=4, dirs=128,
+                 seed=0, quantize=True):
+        R = int(resolution)
+        if R < 16 or R & (R - 1):
+            raise ValueError(f"SlicedWasserstein: resolution must be a power of two >= 16, got {R}")
+        if nhood != 7:
+            raise ValueError("SlicedWasserstein: the kernels gather 7x7 neighbourhoods (nhood=7)")
+        if min(n_images, per_image, repeats, dirs) < 1:
+            raise ValueError("SlicedWasserstein: n_images, per_image, repeats, dirs must be >= 1")
+        self.ops, self.R, self.n_images, self.K = ops, R, int(n_images), int(per_image)
+        self.repeats, self.P, self.seed, self.quantize = int(repeats), int(dirs), int(seed), bool(quantize)
+        self.sizes = [R >> l for l in range(R.bit_length() - 4)]       # R, R/2, .., 16
+        self.device = None               # that of the first images fed
+        self.count = {w: 0 for w in SETS}
+        self.desc = self.dirs = None
+        self._pyr = []
+
+    def _alloc(self, device):
+        self.device = device
+        n = self.n_images * self.K
+        self.desc = {w: [torch.empty(n, DESC, dtype=torch.float32, device=device)
+                         for _ in self.sizes] for w in SETS}
+        self.dirs = draw_directions(self.seed, self.repeats, self.P).to(device)
+
+    def feed(self, which, images):
+        if which not in SETS:
+            raise ValueError(f"SlicedWasserstein.feed: which must be one of {SETS}, got {which!r}")
+        if images.dim() != 4 or tuple(images.shape[1:]) != (3, self.R, self.R):
+            raise ValueError(f"SlicedWasserstein.feed: expected [B, 3, {self.R}, {self.R}], got "
+                             f"{tuple(images.shape)}")
+        B, first = images.shape[0], self.count[which]
+        if first + B > self.n_images:
+            raise ValueError(f"SlicedWasserstein.feed: {first} + {B} {which} images exceed "
+                             f"n_images = {self.n_images}")
+        if B == 0:
+            return
+        if self.desc is None:
+            self._alloc(images.device)
+        x = images.detach().to(torch.float32).contiguous()
+        if not self._pyr or self._pyr[0].shape[0] < B:
+            self._pyr = [torch.empty(B, 3, s, s, dtype=torch.float32, device=self.device)
+                         for s in self.sizes[1:]]
+        pyr = [x] + [t[:B] for t in self._pyr]
+        for l in range(len(self.sizes) - 1):
+            self.ops.swd_pyr_down(pyr[l], pyr[l + 1], self.quantize and l == 0)
+        for l, s in enumerate(self.sizes):
+            pos = draw_positions(self.seed, l, first, B, s, self.K)
+            if int(pos.min()) < 3 or int(pos.max()) >= s - 3:     # the kernel trusts them
+                raise ValueError(f"SlicedWasserstein.feed: patch centres outside [3, {s - 3})")
+            pos = pos.to(self.device)
+            coarse = pyr[l + 1] if l + 1 < len(self.sizes) else None
+            out = self.desc[which][l][first * self.K:(first + B) * self.K]
+            self.ops.swd_descriptors(pyr[l], coarse, pos, out, self.K, self.quantize and l == 0)
+        self.count[which] = first + B
+
+    def result(self):
+        for w in SETS:
+            if self.count[w] != self.n_images:
+                raise RuntimeError(f"SlicedWasserstein.result: {self.count[w]} of {self.n_images} "
+                                   f"{w} images fed")
+        n, P, dev = self.n_images * self.K, self.P, self.device
+        acc = torch.zeros(len(self.sizes), dtype=torch.float32, device=dev)
+        stat = torch.empty(4, 3, dtype=torch.float32, device=dev)
+        proj = [torch.empty(P, n, dtype=torch.float32, device=dev) for _ in SETS]
+        rows = max(1, SORT_INDEX_BYTES // (8 * n))
+        for l in range(len(self.sizes)):
+            for k, w in enumerate(SETS):
+                self.ops.swd_stats(self.desc[w][l], stat[2 * k], stat[2 * k + 1])
+            for r in range(self.repeats):
+                for k, w in enumerate(SETS):
+                    self.ops.swd_project(self.desc[w][l], stat[2 * k], stat[2 * k + 1],
+                                         self.dirs[r], proj[k])
+                for r0 in range(0, P, rows):
+                    a, b = (torch.sort(t[r0:r0 + rows], dim=1).values for t in proj)
+                    self.ops.swd_l1(a, b, n, acc[l:l + 1])
+        vals = [float(v) / (self.repeats * P * n) * 1e3 for v in acc.cpu().tolist()]
+        out = dict(zip(self.sizes, vals))
+        out["avg"] = sum(vals) / len(vals)
+        return out

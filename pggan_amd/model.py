@@ -17,6 +17,8 @@ Differences (deliberate):
   * config `ema_decay` (blank: off) keeps `G_ema`, the exponential moving average of G's
     weights the paper samples from (the reference dropped it): updated inside the Adam_G
     launch, sampled by `sample(z)`, saved beside the reference's files as `G_ema_*.pt`.
+  * config `use_validation` fills in the reference's empty validation(): the paper's sliced
+    Wasserstein distance on the held-out 30 % of the images (pggan_amd.metrics).
 """
 from __future__ import annotations
 
@@ -251,6 +253,7 @@ class ProgressiveGAN:
         R = 4 * 2 ** self.scale_index
         if cfg_get(self.args, "synthetic_data", False):
             self.train_dataset = None
+            self.valid_paths = []
             g = torch.Generator(device=self.device).manual_seed(1000 * self.rank)
             self.synthetic = torch.rand(self.args.batch_per_gpu, 3, R, R, device=self.device,
                                         generator=g) * 2 - 1
@@ -265,6 +268,7 @@ class ProgressiveGAN:
                                f"synthetic_data: True to train on a synthetic batch)")
         n_train = round(len(ds) * 0.7)
         perm = np.random.default_rng(0).permutation(len(ds))
+        self.valid_paths = [ds.paths[i] for i in perm[n_train:]]   # held out: validation()
         ds.paths = [ds.paths[i] for i in perm[:n_train]]
         self.train_dataset = ds
 
@@ -314,11 +318,83 @@ class ProgressiveGAN:
     def loss_collector(self):
         return self._loss_collector
 
+    # ------------------------------------------------------------------ validation
     def set_validation(self):
-        pass
+        """Config `use_validation`: the paper's sliced Wasserstein distance between `swd_images`
+        reals and as many generated images (pggan_amd.metrics), every `valid_cycle` steps."""
+        self._val = None
+        if not cfg_get(self.args, "use_validation", False):
+            return
+        self._val = dict(images=int(cfg_get(self.args, "swd_images", None) or 4096),
+                         seed=int(cfg_get(self.args, "swd_seed", None) or 0))
+        self.valid_cycle = int(cfg_get(self.args, "valid_cycle", None) or self.args.ckpt_cycle)
 
-    def validation(self, *args):
-        pass
+    def _valid_reals(self, R, n, B):
+        """n validation reals at R x R as fp32 [-1, 1] batches of at most B: the images under
+        `valid_dataset_root`, else the held-out 30 % of set_dataset, decoded like the training
+        images without flip or jitter (wrapping around a shorter list); with `synthetic_data`
+        fresh U[-1, 1) draws.  Nothing here is shared with the training loader."""
+        root = cfg_get(self.args, "valid_dataset_root", None)
+        if root:
+            from .data import image_paths
+            paths = sorted(image_paths([root]))
+            if not paths:
+                raise RuntimeError(f"valid_dataset_root: no images under {root}")
+        else:
+            paths = list(getattr(self, "valid_paths", None) or [])
+        if paths:
+            from .data import load_u8
+            for i in range(0, n, B):
+                u8 = np.stack([load_u8(paths[j % len(paths)], R) for j in range(i, min(i + B, n))])
+                x = torch.from_numpy(u8).permute(0, 3, 1, 2).float() / 127.5 - 1
+                yield x.contiguous().to(self.device)
+        elif cfg_get(self.args, "synthetic_data", False):
+            g = torch.Generator().manual_seed(self._val["seed"] + 1)
+            for i in range(0, n, B):
+                yield (torch.rand(min(B, n - i), 3, R, R, generator=g) * 2 - 1).to(self.device)
+        else:
+            raise RuntimeError("validation: no real images (set valid_dataset_root, or train on "
+                               "a dataset so that its held-out 30 % is used)")
+
+    def validation(self, step=0):
+        """Sliced Wasserstein distance x 1e3 per Laplacian level between reals and images of
+        the averaged generator (G itself without `ema_decay`): {R: v, .., 16: v, "avg": v},
+        printed on the master and appended to {save_root}/{run_id}/swd.csv as
+        step,scale,levels..,avg.  None with `use_validation` off and below 16 x 16.  Reads the
+        generator through sample() only; draws from private generators."""
+        val = getattr(self, "_val", None)
+        if val is None:
+            return None
+        master = cfg_get(self.args, "isMaster", False)
+        R = 4 * 2 ** self.scale_index
+        if R < 16:
+            if master:
+                print(f"step {step}: SWD is undefined below 16x16 (stage is {R}x{R})")
+            return None
+        from . import _lib
+        from .metrics import SlicedWasserstein
+        ops = val.get("ops")
+        if ops is None:
+            ops = val["ops"] = (type(self).ops_factory or _lib.HipOps)(torch.float32)
+        n, B = val["images"], int(self.args.batch_per_gpu)
+        swd = SlicedWasserstein(ops, R, n, seed=val["seed"])
+        for x in self._valid_reals(R, n, B):
+            swd.feed("real", x)
+        g = torch.Generator().manual_seed(val["seed"])
+        for i in range(0, n, B):     # always whole batches: one sampling engine shape
+            z = torch.randn(B, self.args.latent_dim, generator=g).to(self.device)
+            swd.feed("fake", self.sample(z, ema=self.G_ema is not None)[:n - i])
+        out = swd.result()
+        levels = [out[k] for k in swd.sizes]
+        if master:
+            print(f"step {step}: SWD x1e3 " + " ".join(f"{k}:{out[k]:.4f}" for k in swd.sizes) +
+                  f" avg:{out['avg']:.4f}")
+        d = f"{self.args.save_root}/{self.args.run_id}"
+        os.makedirs(d, exist_ok=True)
+        with open(f"{d}/swd.csv", "a") as f:
+            f.write(",".join([str(step), str(self.scale_index)] +
+                             [repr(v) for v in levels + [out["avg"]]]) + "\n")
+        return out
 
     # ------------------------------------------------------------------ step
     def _engine(self, B):

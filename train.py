@@ -81,6 +81,8 @@ def train(args):
                 model.save_image(images, step)
             if step % args.ckpt_cycle == 0:
                 model.save_checkpoint(step)
+            if args.get("use_validation") and step % model.valid_cycle == 0:
+                model.validation(step)
         step += 1
 
 
