@@ -81,9 +81,9 @@ size_t pg_scratch_bytes(void);
                                  with POOL the mask applies before pooling; may be combined
                                  with X_BITS (input and output masks both from bits) */
 #define PG_CONV_X_BITS 512    /* x is masked on load by lrelu'(xbits) at conv resolution
-                                 (pg_conv3x3_fwd_ex; xb_cs = bytes per pixel) */
+                                 (the xbits operand; xb_cs = bytes per pixel) */
 #define PG_CONV_GZ_BITS 1024  /* wgrad: gz is at H/2 x W/2 and the effective gradient is
-                                 up2(gz) * lrelu'(gzbits) (pg_conv3x3_wgrad_ex) */
+                                 up2(gz) * lrelu'(gzbits) (the gzbits operand) */
 /* PixelNorm + LReLU backward fused into an input-gradient conv (bf16, H,W >= 16 kernel; query
  * pg_conv3x3_supported): with v the conv result = dL/dy of a PG_CONV_PIXNORM output y, the
  * launch writes dL/du = r * (v - y * mean_c(y * v)) * lrelu'(y), u the pre-norm activation
@@ -151,13 +151,11 @@ int pg_conv3x3_pack_batch(int dtype, int n, const pg_pack_item* items, int max_t
  * over input-channel chunks for small-spatial convs (deterministic: partial slabs + a
  * reduction/epilogue kernel); NULL or too small -> single pass. */
 size_t pg_conv3x3_workspace_size(const pg_conv_desc* d);
-int pg_conv3x3_fwd(int dtype, const pg_conv_desc* d, const void* x, const void* wpk,
-                   const float* bias, const void* aux, void* y, void* y2, void* ws,
-                   size_t ws_bytes, void* stream);
-/* pg_conv3x3_fwd with the input-mask bit tensor of PG_CONV_X_BITS */
-int pg_conv3x3_fwd_ex(int dtype, const pg_conv_desc* d, const void* x, const void* xbits,
-                      const void* wpk, const float* bias, const void* aux, void* y, void* y2,
-                      void* ws, size_t ws_bytes, void* stream);
+/* xbits: the input-mask bit tensor of PG_CONV_X_BITS (bf16), NULL without that flag.  The
+ * RGBW / RGBD / RGBO flags are refused here: they have their own entry points below. */
+int pg_conv3x3_fwd(int dtype, const pg_conv_desc* d, const void* x, const void* xbits,
+                   const void* wpk, const float* bias, const void* aux, void* y, void* y2,
+                   void* ws, size_t ws_bytes, void* stream);
 /* The input-gradient conv of PG_CONV_RGBW (d->flags includes it, y is not written): x, wpk,
  * aux as pg_conv3x3_fwd; img the fromRGB layer's input image, s its He constant, dw [C*3] /
  * db [C] the fromRGB weight / bias gradients (accumulated), scratch a PG_SCRATCH_BYTES
@@ -191,14 +189,12 @@ int pg_conv3x3_supported(int dtype, const pg_conv_desc* d, size_t ws_bytes);
 /* ws: optional fp32 workspace (>= pg_conv3x3_wgrad_workspace_size bytes).  When the pixel
  * range is split over workgroups the partial sums go to per-split slabs of ws and a
  * second kernel adds them into dw/db; NULL or too small -> fp32 atomics per split. */
+/* gzbits: NULL, or with PG_CONV_GZ_BITS (bf16 only) the sign bits at full resolution (xb_cs
+ * bytes per pixel) of a gz given at half resolution (channel stride y_cs). */
 size_t pg_conv3x3_wgrad_workspace_size(int dtype, const pg_conv_desc* d);
-int pg_conv3x3_wgrad(int dtype, const pg_conv_desc* d, const void* x, const void* gz, float scale,
-                     float* dw, float* db, void* ws, size_t ws_bytes, void* stream);
-/* pg_conv3x3_wgrad with PG_CONV_GZ_BITS: gz at half resolution (channel stride y_cs),
- * gzbits at full resolution (xb_cs bytes per pixel); bf16 only */
-int pg_conv3x3_wgrad_ex(int dtype, const pg_conv_desc* d, const void* x, const void* gz,
-                        const void* gzbits, float scale, float* dw, float* db, void* ws,
-                        size_t ws_bytes, void* stream);
+int pg_conv3x3_wgrad(int dtype, const pg_conv_desc* d, const void* x, const void* gz,
+                     const void* gzbits, float scale, float* dw, float* db, void* ws,
+                     size_t ws_bytes, void* stream);
 /* bias gradient, accumulates: db[c] += scale * sum_p g[p][c] */
 int pg_bias_grad(int dtype, int npix, int C, int cs, const void* g, float scale, float* db,
                  void* scratch, void* stream);
@@ -210,19 +206,16 @@ int pg_pixnorm_lrelu_bwd(int dtype, int npix, int C, int cs, const void* u, cons
                          float slope, int apply_mask, void* gz, void* stream);
 
 /* ---- elementwise helpers (NHWC, channel stride cs) */
-/* out[p] = scale * g[ups ? p/2 : p] * (y ? lrelu'(y[p]) : 1)   (avg-pool backward, lib/blocks.py:193) */
 /* the same backward from the fused conv's outputs (PG_CONV_PIXNORM): y = normalised
  * activation, r = per-pixel factor (fp32 [npix]); u = y / r is never stored */
 int pg_pixnorm_lrelu_bwd_y(int dtype, int npix, int C, int cs, const void* y, const float* r,
                            const void* gy, float slope, void* gz, void* stream);
+/* out[p] = scale * g[ups ? p/2 : p] * (y ? lrelu'(y[p]) : 1)   (avg-pool backward, lib/blocks.py:193)
+ * bits: NULL, or (bf16, C % 8 == 0) the lrelu' operand as sign bits, uint8 [B][H][W][C / 8]
+ * (PG_CONV_Y2_BITS of the pooled conv that produced it) instead of the activation y */
 int pg_unpool_mask(int dtype, int B, int H, int W, int C, int g_cs, const void* g, int y_cs,
-                   const void* y, float scale, float slope, int ups, int out_cs, void* out,
-                   void* stream);
-/* pg_unpool_mask (bf16, C % 8 == 0) with the lrelu' operand as sign bits, uint8 [B][H][W][C / 8]
- * (PG_CONV_Y2_BITS of the pooled conv that produced it) instead of the bf16 activation y */
-int pg_unpool_mask_bits(int dtype, int B, int H, int W, int C, int g_cs, const void* g,
-                        const void* bits, float scale, float slope, int ups, int out_cs, void* out,
-                        void* stream);
+                   const void* y, const void* bits, float scale, float slope, int ups, int out_cs,
+                   void* out, void* stream);
 /* 2x2 average pool (lib/utils.py:120-124), input B x H x W */
 int pg_avgpool2(int dtype, int B, int H, int W, int C, int x_cs, const void* x, int y_cs, void* y,
                 void* stream);
@@ -241,31 +234,17 @@ int pg_rgb_out_bwd(int dtype, int B, int R, int C, int x_cs, const void* x, cons
                    float c, int Cp, int xp_cs, const void* xp, const float* wp, float cp,
                    float alpha, const float* gimg, void* gx, void* gxp, float* dw, float* db,
                    float* dwp, float* dbp, void* scratch, void* stream);
-/* fromRGB: y = lrelu(c*(W . img_in + b)), img_in = down ? avgpool2(img) : img  (img NCHW fp32);
- * R = output resolution.  b == NULL -> no bias; mask_y != NULL -> tangent mode:
- * y = c*(W . img_in) * lrelu'(mask_y) (no activation) */
 /* the toRGB input gradient fused with the PixelNorm + LReLU backward of its input y (the level's
  * PG_CONV_PIXNORM output, r its per-pixel factor fp32 [B*R*R]): gz = r (v - y mean_c(y v))
  * lrelu'(y), v = c W^T gimg (pg_rgb_out_bwd's gx then pg_pixnorm_lrelu_bwd_y, without v's round
- * trip through HBM); C 16 or 32, alpha = 1 (no fade-in branch) */
+ * trip through HBM); C 16 or 32, alpha = 1 (no fade-in branch).  dw != NULL: also the toRGB
+ * weight / bias gradients of the same pass (dw[i][k] += c sum gimg[i] y[k], db[i] += c sum
+ * gimg[i] if db; scratch: the stream's PG_SCRATCH_BYTES reduction scratch, else may be NULL): y
+ * and gimg are streamed once for both (lib/blocks.py toRGB, pggan/nets.py:140-156) */
 int pg_rgb_out_bwd_pn(int dtype, int B, int R, int C, int y_cs, const void* y, const float* r,
                       const float* w, float c, const float* gimg, float slope, int gz_cs, void* gz,
-                      void* stream);
-/* pg_rgb_out_bwd_pn with the toRGB weight / bias gradients of the same pass (dw[i][k] +=
- * c sum gimg[i] y[k], db[i] += c sum gimg[i]; scratch: the stream's PG_SCRATCH_BYTES reduction
- * scratch): y and gimg are streamed once for both (lib/blocks.py toRGB, pggan/nets.py:140-156) */
-int pg_rgb_out_bwd_pn_wg(int dtype, int B, int R, int C, int y_cs, const void* y, const float* r,
-                         const float* w, float c, const float* gimg, float slope, int gz_cs,
-                         void* gz, float* dw, float* db, void* scratch, void* stream);
-int pg_from_rgb(int dtype, int B, int R, int C, const float* img, int down, const float* w,
-                const float* b, float c, float slope, const void* mask_y, int y_cs, void* y,
-                void* stream);
-/* backward: gimg[b][i][p] += c * sum_o gz[p(/2)][o] W[o][i] * (down ? 0.25 : 1) (if gimg);
- * dw[o][i] += c sum gz*img_in, db[o] += c sum gz (if dw/db) */
-int pg_from_rgb_bwd(int dtype, int B, int R, int C, const float* img, int down, const float* w,
-                    float c, int gz_cs, const void* gz, float* gimg, float* dw, float* db,
-                    void* scratch, void* stream);
-/* An image operand of the fromRGB layers given as a per-sample mix instead of a tensor:
+                      float* dw, float* db, void* scratch, void* stream);
+/* An image operand of the fromRGB layers, a tensor (x0 alone) or a per-sample mix:
  * img[b] = a[b] * x0[b] + c[b] * x1[b] (NCHW fp32; a, c: DEVICE arrays of B floats; x1 and c
  * may be NULL; a == NULL means img = x0).  The gradient-penalty passes read the interpolated
  * image eps x_real + (1 - eps) x_fake (pggan/loss.py:75) and the penalty-weighted input
@@ -276,26 +255,26 @@ typedef struct {
   const float* a;
   const float* c;
 } pg_img_src;
-/* pg_from_rgb with the image operand as a pg_img_src */
-int pg_from_rgb_src(int dtype, int B, int R, int C, const pg_img_src* img, int down, const float* w,
-                    const float* b, float c, float slope, const void* mask_y, int y_cs, void* y,
-                    void* stream);
-/* pg_from_rgb_src (bf16, C % 8 == 0, C <= 64) with the lrelu sign bits as an operand instead of
- * a bf16 activation: ybits != NULL (forward) also writes the bits of the result y > 0, uint8
+/* fromRGB: y = lrelu(c*(W . img_in + b)), img_in = down ? avgpool2(img) : img; R = output
+ * resolution.  b == NULL -> no bias; mask_y != NULL -> tangent mode: y = c*(W . img_in) *
+ * lrelu'(mask_y) (no activation).
+ * The lrelu sign bits as an operand instead of a bf16 activation (bf16, C % 8 == 0, C <= 64,
+ * mask_y NULL): ybits != NULL (forward) also writes the bits of the result y > 0, uint8
  * [B][R][R][C / 8] (channel o at byte o / 8, bit o % 8); mask_bits != NULL (the R1 tangent) masks
- * with those bits where pg_from_rgb reads mask_y (16x fewer bytes: 134 MB -> 8.4 MB per launch at
+ * with those bits where mask_y would be read (16x fewer bytes: 134 MB -> 8.4 MB per launch at
  * 1024^2, 16 channels, B = 4).  At most one of the two. */
-int pg_from_rgb_bits(int dtype, int B, int R, int C, const pg_img_src* img, int down,
-                     const float* w, const float* b, float c, float slope, const void* mask_bits,
-                     int y_cs, void* y, void* ybits, void* stream);
-/* pg_from_rgb_bwd with the image operand (of the weight gradient) as a pg_img_src, and for the
- * input gradient: gimg_overwrite = 1 writes gimg instead of accumulating into it; norms !=
- * NULL: norms[b] += sum over sample b of the final gimg^2 (the penalties' per-sample squared
- * norms, fused into the pass that writes the input gradient) */
-int pg_from_rgb_bwd_src(int dtype, int B, int R, int C, const pg_img_src* img, int down,
-                        const float* w, float c, int gz_cs, const void* gz, float* gimg,
-                        int gimg_overwrite, float* norms, float* dw, float* db, void* scratch,
-                        void* stream);
+int pg_from_rgb(int dtype, int B, int R, int C, const pg_img_src* img, int down, const float* w,
+                const float* b, float c, float slope, const void* mask_y, const void* mask_bits,
+                int y_cs, void* y, void* ybits, void* stream);
+/* backward: gimg[b][i][p] += c * sum_o gz[p(/2)][o] W[o][i] * (down ? 0.25 : 1) (if gimg;
+ * gimg_overwrite = 1 writes gimg instead of accumulating into it); norms != NULL: norms[b] +=
+ * sum over sample b of the final gimg^2 (the penalties' per-sample squared norms, fused into
+ * the pass that writes the input gradient); dw[o][i] += c sum gz*img_in, db[o] += c sum gz (if
+ * dw / db; img may be NULL without them) */
+int pg_from_rgb_bwd(int dtype, int B, int R, int C, const pg_img_src* img, int down,
+                    const float* w, float c, int gz_cs, const void* gz, float* gimg,
+                    int gimg_overwrite, float* norms, float* dw, float* db, void* scratch,
+                    void* stream);
 /* The penalty and the tangent-pass scale from the per-sample squared norms n_b of g = dD/dx:
  * mode 0 (R1, lib/loss.py:125-135): loss_out[0] += 0.5 * sum_b n_b / B, scale_b = 1 / B;
  * mode 1 (WGAN-GP, pggan/loss.py:81-87): loss_out[0] += w * sum_b (sqrt(n_b) - 1)^2,
@@ -323,21 +302,17 @@ typedef struct {
   int flags;
   float scale, slope;
 } pg_linear_desc;
+/* ws: optional fp32 workspace (>= pg_linear_workspace_size bytes; pass 0 = fwd, 1 = dgrad) for
+ * the bf16 split-reduction forms of the two passes below (deterministic: fp32 partials of weight
+ * slices in ws, then a small epilogue kernel).  NULL or too small (or the fp32 mode): one pass. */
+size_t pg_linear_workspace_size(int dtype, const pg_linear_desc* d, int pass);
 int pg_linear_fwd(int dtype, const pg_linear_desc* d, const void* x, const float* w,
-                  const float* b, const void* aux, void* y, void* stream);
+                  const float* b, const void* aux, void* y, void* ws, size_t ws_bytes,
+                  void* stream);
 /* gx[b][k] = scale * sum_n gy[b][n] W[n][k]  (* lrelu'(aux[b][k]) if PG_LIN_MASK); flags
  * IN_CHW/F32_IN describe gx, OUT_CHW/F32_OUT describe gy */
 int pg_linear_dgrad(int dtype, const pg_linear_desc* d, const void* gy, const float* w,
-                    const void* aux, void* gx, void* stream);
-/* bf16 split-reduction forms of the two passes above (deterministic: fp32 partials of
- * weight slices in ws, then a small epilogue kernel); pass 0 = fwd, 1 = dgrad.  A NULL or
- * too small ws (or the fp32 mode) falls back to pg_linear_fwd / pg_linear_dgrad. */
-size_t pg_linear_workspace_size(int dtype, const pg_linear_desc* d, int pass);
-int pg_linear_fwd_ws(int dtype, const pg_linear_desc* d, const void* x, const float* w,
-                     const float* b, const void* aux, void* y, void* ws, size_t ws_bytes,
-                     void* stream);
-int pg_linear_dgrad_ws(int dtype, const pg_linear_desc* d, const void* gy, const float* w,
-                       const void* aux, void* gx, void* ws, size_t ws_bytes, void* stream);
+                    const void* aux, void* gx, void* ws, size_t ws_bytes, void* stream);
 /* accumulates dw[n][k] += scale sum_b gy[b][n] x[b][k]; db[n] += scale sum_b gy[b][n] */
 int pg_linear_wgrad(int dtype, const pg_linear_desc* d, const void* x, const void* gy, float* dw,
                     float* db, void* stream);
@@ -365,10 +340,8 @@ int pg_drift_loss(int B, const float* logits, float w, float* loss_out, float* u
 /* R1 = 0.5 * mean_b sum g^2 accumulated into r1_out[0]; gbar = g / B  (g: [n] fp32, B samples) */
 int pg_r1_penalty(int B, size_t n, const float* g, float* r1_out, float* gbar, void* scratch,
                   void* stream);
-/* WGAN-GP optional mode (pggan/loss.py:54-92): interp = eps*xr + (1-eps)*xf (per-sample eps) */
-int pg_gp_interp(int B, size_t per, const float* xr, const float* xf, const float* eps,
-                 float* out, void* stream);
-/* gp = w * sum_b (||g_b|| - 1)^2 -> gp_out[0] (accumulate); gbar_b = w*2*(||g_b||-1)/||g_b|| g_b;
+/* WGAN-GP optional mode (pggan/loss.py:54-92):
+ * gp = w * sum_b (||g_b|| - 1)^2 -> gp_out[0] (accumulate); gbar_b = w*2*(||g_b||-1)/||g_b|| g_b;
  * norms[B] workspace */
 int pg_gp_penalty(int B, size_t per, const float* g, float w, float* gp_out, float* norms,
                   float* gbar, void* scratch, void* stream);

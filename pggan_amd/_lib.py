@@ -96,8 +96,8 @@ _SIGS = {
     "pg_conv3x3_pack": ([_I, _I, _I, _I, _VP, _F, _VP, _VP], _I),
     "pg_conv3x3_pack_batch": ([_I, _I, _VP, _I, _VP], _I),
     "pg_conv3x3_workspace_size": ([ctypes.POINTER(ConvDesc)], _SZ),
-    "pg_conv3x3_fwd": ([_I, ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP],
-                       _I),
+    "pg_conv3x3_fwd": ([_I, ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ,
+                        _VP], _I),
     "pg_conv3x3_supported": ([_I, ctypes.POINTER(ConvDesc), _SZ], _I),
     "pg_conv3x3_rgbw": ([_I, ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _F, _VP, _VP, _VP, _VP],
                         _I),
@@ -105,53 +105,38 @@ _SIGS = {
                          _VP, _VP], _I),
     "pg_conv3x3_rgbo": ([_I, ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _F, _VP,
                          _VP], _I),
-    "pg_conv3x3_fwd_ex": ([_I, ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
-                           _SZ, _VP], _I),
-    "pg_conv3x3_wgrad_ex": ([_I, ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _F, _VP, _VP, _VP, _SZ,
-                             _VP], _I),
     "pg_conv3x3_wgrad_workspace_size": ([_I, ctypes.POINTER(ConvDesc)], _SZ),
-    "pg_conv3x3_wgrad": ([_I, ctypes.POINTER(ConvDesc), _VP, _VP, _F, _VP, _VP, _VP, _SZ, _VP],
-                         _I),
+    "pg_conv3x3_wgrad": ([_I, ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _F, _VP, _VP, _VP, _SZ,
+                          _VP], _I),
     "pg_bias_grad": ([_I, _I, _I, _I, _VP, _F, _VP, _VP, _VP], _I),
     "pg_pixnorm_fwd": ([_I, _I, _I, _I, _VP, _VP, _VP], _I),
     "pg_pixnorm_lrelu_bwd": ([_I, _I, _I, _I, _VP, _VP, _F, _I, _VP, _VP], _I),
     "pg_pixnorm_lrelu_bwd_y": ([_I, _I, _I, _I, _VP, _VP, _VP, _F, _VP, _VP], _I),
-    "pg_unpool_mask": ([_I, _I, _I, _I, _I, _I, _VP, _I, _VP, _F, _F, _I, _I, _VP, _VP], _I),
-    "pg_unpool_mask_bits": ([_I, _I, _I, _I, _I, _I, _VP, _VP, _F, _F, _I, _I, _VP, _VP], _I),
+    "pg_unpool_mask": ([_I, _I, _I, _I, _I, _I, _VP, _I, _VP, _VP, _F, _F, _I, _I, _VP, _VP], _I),
     "pg_avgpool2": ([_I, _I, _I, _I, _I, _I, _VP, _I, _VP, _VP], _I),
     "pg_blend": ([_I, _SZ, _F, _VP, _F, _VP, _VP, _VP], _I),
     "pg_rgb_out": ([_I, _I, _I, _I, _I, _VP, _VP, _VP, _F, _I, _I, _VP, _VP, _VP, _F, _F, _VP,
                     _VP], _I),
     "pg_rgb_out_bwd": ([_I, _I, _I, _I, _I, _VP, _VP, _F, _I, _I, _VP, _VP, _F, _F, _VP, _VP,
                         _VP, _VP, _VP, _VP, _VP, _VP, _VP], _I),
-    "pg_from_rgb": ([_I, _I, _I, _I, _VP, _I, _VP, _VP, _F, _F, _VP, _I, _VP, _VP], _I),
-    "pg_from_rgb_bwd": ([_I, _I, _I, _I, _VP, _I, _VP, _F, _I, _VP, _VP, _VP, _VP, _VP, _VP], _I),
+    "pg_from_rgb": ([_I, _I, _I, _I, ctypes.POINTER(ImgSrcDesc), _I, _VP, _VP, _F, _F, _VP, _VP,
+                     _I, _VP, _VP, _VP], _I),
+    "pg_from_rgb_bwd": ([_I, _I, _I, _I, ctypes.POINTER(ImgSrcDesc), _I, _VP, _F, _I, _VP, _VP, _I,
+                         _VP, _VP, _VP, _VP, _VP], _I),
     "pg_img_fade": ([_I, _I, _I, _VP, _F, _VP, _VP], _I),
-    "pg_from_rgb_src": ([_I, _I, _I, _I, ctypes.POINTER(ImgSrcDesc), _I, _VP, _VP, _F, _F, _VP, _I,
-                         _VP, _VP], _I),
-    "pg_rgb_out_bwd_pn": ([_I, _I, _I, _I, _I, _VP, _VP, _VP, _F, _VP, _F, _I, _VP, _VP], _I),
-    "pg_rgb_out_bwd_pn_wg": ([_I, _I, _I, _I, _I, _VP, _VP, _VP, _F, _VP, _F, _I, _VP, _VP, _VP,
-                              _VP, _VP], _I),
-    "pg_from_rgb_bits": ([_I, _I, _I, _I, ctypes.POINTER(ImgSrcDesc), _I, _VP, _VP, _F, _F, _VP,
-                          _I, _VP, _VP, _VP], _I),
-    "pg_from_rgb_bwd_src": ([_I, _I, _I, _I, ctypes.POINTER(ImgSrcDesc), _I, _VP, _F, _I, _VP, _VP,
-                             _I, _VP, _VP, _VP, _VP, _VP], _I),
+    "pg_rgb_out_bwd_pn": ([_I, _I, _I, _I, _I, _VP, _VP, _VP, _F, _VP, _F, _I, _VP, _VP, _VP, _VP,
+                           _VP], _I),
     "pg_penalty_scale": ([_I, _I, _VP, _F, _VP, _VP, _VP], _I),
-    "pg_linear_fwd": ([_I, ctypes.POINTER(LinearDesc), _VP, _VP, _VP, _VP, _VP, _VP], _I),
-    "pg_linear_dgrad": ([_I, ctypes.POINTER(LinearDesc), _VP, _VP, _VP, _VP, _VP], _I),
+    "pg_linear_fwd": ([_I, ctypes.POINTER(LinearDesc), _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP], _I),
+    "pg_linear_dgrad": ([_I, ctypes.POINTER(LinearDesc), _VP, _VP, _VP, _VP, _VP, _SZ, _VP], _I),
     "pg_linear_wgrad": ([_I, ctypes.POINTER(LinearDesc), _VP, _VP, _VP, _VP, _VP], _I),
     "pg_linear_workspace_size": ([_I, ctypes.POINTER(LinearDesc), _I], _SZ),
-    "pg_linear_fwd_ws": ([_I, ctypes.POINTER(LinearDesc), _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _VP],
-                         _I),
-    "pg_linear_dgrad_ws": ([_I, ctypes.POINTER(LinearDesc), _VP, _VP, _VP, _VP, _VP, _SZ, _VP],
-                           _I),
     "pg_mbstd_fwd": ([_I, _I, _I, _I, _I, _VP, _I, _VP, _VP], _I),
     "pg_mbstd_bwd": ([_I, _I, _I, _I, _I, _VP, _I, _VP, _VP, _VP], _I),
     "pg_mbstd_r1": ([_I, _I, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP], _I),
     "pg_bce_loss": ([_I, _VP, _I, _F, _VP, _VP, _VP, _VP], _I),
     "pg_r1_penalty": ([_I, _SZ, _VP, _VP, _VP, _VP, _VP], _I),
     "pg_drift_loss": ([_I, _VP, _F, _VP, _VP, _VP], _I),
-    "pg_gp_interp": ([_I, _SZ, _VP, _VP, _VP, _VP, _VP], _I),
     "pg_gp_penalty": ([_I, _SZ, _VP, _F, _VP, _VP, _VP, _VP, _VP], _I),
     "pg_mul_add": ([_SZ, _VP, _VP, _VP, _VP, _VP], _I),
     "pg_adam": ([_SZ, _VP, _VP, _VP, _VP, _F, _F, _F, _F, _I, _VP], _I),
@@ -423,9 +408,8 @@ class HipOps:
                      y2.shape[-1] if y2 is not None else 0, flags, slope, out_scale,
                      xbits.shape[-1] if xbits is not None else 0)
         wsb = ws.numel() * ws.element_size() if ws is not None else 0
-        self._chk(self.lib.pg_conv3x3_fwd_ex(self._dt(y), ctypes.byref(d), _p(x), _p(xbits),
-                                             _p(wpk), _p(bias), _p(aux), _p(y), _p(y2), _p(ws),
-                                             wsb, self._s()),
+        self._chk(self.lib.pg_conv3x3_fwd(self._dt(y), ctypes.byref(d), _p(x), _p(xbits), _p(wpk),
+                                          _p(bias), _p(aux), _p(y), _p(y2), _p(ws), wsb, self._s()),
                   "conv3x3_fwd")
 
     def conv3x3_rgbw(self, x, wpk, *, B, H, W, cin, cout, flags, aux, img, s, dw, db,
@@ -492,9 +476,9 @@ class HipOps:
         d = ConvDesc(B, H, W, cin, cout, x.shape[-1], gz.shape[-1], 0, 0, fl, slope, 1.0,
                      gzbits.shape[-1] if gzbits is not None else 0)
         wsb = ws.numel() * ws.element_size() if ws is not None else 0
-        self._chk(self.lib.pg_conv3x3_wgrad_ex(self._dt(gz), ctypes.byref(d), _p(x), _p(gz),
-                                               _p(gzbits), scale, _p(dw), _p(db), _p(ws), wsb,
-                                               self._s()),
+        self._chk(self.lib.pg_conv3x3_wgrad(self._dt(gz), ctypes.byref(d), _p(x), _p(gz),
+                                            _p(gzbits), scale, _p(dw), _p(db), _p(ws), wsb,
+                                            self._s()),
                   "conv3x3_wgrad")
 
     def bias_grad(self, g, db, C, scale):
@@ -530,15 +514,10 @@ class HipOps:
     def unpool_mask(self, g, y, out, *, B, H, W, C, scale, slope, ups, bits=None):
         """bits: the lrelu' operand as sign bits (uint8 [B, H, W, C / 8]) instead of y."""
         self._cuda(g, y, out, bits)
-        if bits is not None:
-            self._chk(self.lib.pg_unpool_mask_bits(self._dt(out), B, H, W, C, g.shape[-1], _p(g),
-                                                   _p(bits), scale, slope, 1 if ups else 0,
-                                                   out.shape[-1], _p(out), self._s()),
-                      "unpool_mask_bits")
-            return
         self._chk(self.lib.pg_unpool_mask(self._dt(out), B, H, W, C, g.shape[-1], _p(g),
-                                          y.shape[-1] if y is not None else 0, _p(y), scale, slope,
-                                          1 if ups else 0, out.shape[-1], _p(out), self._s()),
+                                          y.shape[-1] if y is not None else 0, _p(y), _p(bits),
+                                          scale, slope, 1 if ups else 0, out.shape[-1], _p(out),
+                                          self._s()),
                   "unpool_mask")
 
     def avgpool2(self, x, y, *, B, H, W, C):
@@ -569,17 +548,11 @@ class HipOps:
 
     def rgb_out_bwd_pn(self, y, r, w, c, gimg, gz, *, B, R, C, slope, dw=None, db=None):
         """toRGB input gradient + the PixelNorm / LReLU backward of its input y (pg_rgb_out_bwd_pn);
-        with dw / db also the toRGB weight / bias gradients of the same pass (_wg)."""
-        if dw is not None:
-            self._cuda(y, r, w, gimg, gz, dw, db)
-            self._chk(self.lib.pg_rgb_out_bwd_pn_wg(self._dt(y), B, R, C, y.shape[-1], _p(y), _p(r),
-                                                    _p(w), c, _p(gimg), slope, gz.shape[-1], _p(gz),
-                                                    _p(dw), _p(db), self._scr(), self._s()),
-                      "rgb_out_bwd_pn_wg")
-            return
-        self._cuda(y, r, w, gimg, gz)
+        with dw / db also the toRGB weight / bias gradients of the same pass."""
+        self._cuda(y, r, w, gimg, gz, dw, db)
         self._chk(self.lib.pg_rgb_out_bwd_pn(self._dt(y), B, R, C, y.shape[-1], _p(y), _p(r), _p(w), c,
-                                             _p(gimg), slope, gz.shape[-1], _p(gz), self._s()),
+                                             _p(gimg), slope, gz.shape[-1], _p(gz), _p(dw), _p(db),
+                                             self._scr() if dw is not None else None, self._s()),
                   "rgb_out_bwd_pn")
 
     def _src(self, img):
@@ -597,18 +570,12 @@ class HipOps:
     def from_rgb(self, img, w, b, c, y, *, B, R, C, down, slope=0.2, mask_y=None, ybits=None,
                  mask_bits=None):
         """ybits: also write the lrelu sign bits of y (uint8 [B, R, R, C / 8]); mask_bits: the
-        tangent's lrelu' mask from those bits instead of mask_y (pg_from_rgb_bits)."""
+        tangent's lrelu' mask from those bits instead of mask_y."""
         self._cuda(w, b, y, mask_y, ybits, mask_bits)
         src = self._src(img)
-        if ybits is not None or mask_bits is not None:
-            self._chk(self.lib.pg_from_rgb_bits(self._dt(y), B, R, C, ctypes.byref(src),
-                                                1 if down else 0, _p(w), _p(b), c, slope,
-                                                _p(mask_bits), y.shape[-1], _p(y), _p(ybits),
-                                                self._s()), "from_rgb_bits")
-            return
-        self._chk(self.lib.pg_from_rgb_src(self._dt(y), B, R, C, ctypes.byref(src), 1 if down else 0,
-                                           _p(w), _p(b), c, slope, _p(mask_y), y.shape[-1], _p(y),
-                                           self._s()), "from_rgb")
+        self._chk(self.lib.pg_from_rgb(self._dt(y), B, R, C, ctypes.byref(src), 1 if down else 0,
+                                       _p(w), _p(b), c, slope, _p(mask_y), _p(mask_bits),
+                                       y.shape[-1], _p(y), _p(ybits), self._s()), "from_rgb")
 
     def from_rgb_bwd(self, gz, w, c, *, B, R, C, down, img=None, gimg=None, dw=None, db=None,
                      gimg_overwrite=False, norms=None):
@@ -616,11 +583,11 @@ class HipOps:
         of squares of the final gimg (the penalties' squared norms)."""
         self._cuda(gz, w, gimg, dw, db, norms)
         src = self._src(img)
-        self._chk(self.lib.pg_from_rgb_bwd_src(self._dt(gz), B, R, C,
-                                               ctypes.byref(src) if src is not None else None,
-                                               1 if down else 0, _p(w), c, gz.shape[-1], _p(gz),
-                                               _p(gimg), 1 if gimg_overwrite else 0, _p(norms),
-                                               _p(dw), _p(db), self._scr(), self._s()), "from_rgb_bwd")
+        self._chk(self.lib.pg_from_rgb_bwd(self._dt(gz), B, R, C,
+                                           ctypes.byref(src) if src is not None else None,
+                                           1 if down else 0, _p(w), c, gz.shape[-1], _p(gz),
+                                           _p(gimg), 1 if gimg_overwrite else 0, _p(norms),
+                                           _p(dw), _p(db), self._scr(), self._s()), "from_rgb_bwd")
 
     def penalty_scale(self, mode, norms, w, loss, scale):
         """mode "r1" / "wgan-gp": the penalty into loss[0] and the per-sample tangent scale
@@ -660,16 +627,16 @@ class HipOps:
         N, K = w.shape
         d = self._lin(B, K, N, flags, scale, slope, x, y)
         ws, wsb = self._lin_ws(d, 0, y.device)
-        self._chk(self.lib.pg_linear_fwd_ws(self.dt, ctypes.byref(d), _p(x), _p(w), _p(b), _p(aux),
-                                            _p(y), _p(ws), wsb, self._s()), "linear_fwd")
+        self._chk(self.lib.pg_linear_fwd(self.dt, ctypes.byref(d), _p(x), _p(w), _p(b), _p(aux),
+                                         _p(y), _p(ws), wsb, self._s()), "linear_fwd")
 
     def linear_dgrad(self, gy, w, gx, *, B, flags, scale, slope=0.2, aux=None):
         self._cuda(gy, w, gx, aux)
         N, K = w.shape
         d = self._lin(B, K, N, flags, scale, slope, gx, gy)
         ws, wsb = self._lin_ws(d, 1, gx.device)
-        self._chk(self.lib.pg_linear_dgrad_ws(self.dt, ctypes.byref(d), _p(gy), _p(w), _p(aux),
-                                              _p(gx), _p(ws), wsb, self._s()), "linear_dgrad")
+        self._chk(self.lib.pg_linear_dgrad(self.dt, ctypes.byref(d), _p(gy), _p(w), _p(aux),
+                                           _p(gx), _p(ws), wsb, self._s()), "linear_dgrad")
 
     def linear_wgrad(self, x, gy, dw, db, *, B, flags, scale):
         self._cuda(x, gy, dw, db)
@@ -710,12 +677,6 @@ class HipOps:
         self._cuda(g, r1, gbar)
         self._chk(self.lib.pg_r1_penalty(B, g.numel(), _p(g), _p(r1), _p(gbar), self._scr(),
                                          self._s()), "r1_penalty")
-
-    def gp_interp(self, xr, xf, eps, out):
-        self._cuda(xr, xf, eps, out)
-        B = xr.shape[0]
-        self._chk(self.lib.pg_gp_interp(B, xr.numel() // B, _p(xr), _p(xf), _p(eps), _p(out),
-                                        self._s()), "gp_interp")
 
     def gp_penalty(self, g, w, gp, norms, gbar):
         self._cuda(g, gp, norms, gbar)

@@ -355,6 +355,17 @@ inline void pg_launch(void (*k)(KArgs...), dim3 g, dim3 b, unsigned lds, hipStre
 
 static inline int pg_cdiv(int a, int b) { return (a + b - 1) / b; }
 
+// Runtime dtype -> storage type: calls f with a value of float (PG_F32) or bf16_t (PG_BF16) and
+// returns its status, as in `[&](auto t) { using T = decltype(t); ...; return PG_OK; }`.  Any
+// other dtype is PG_ERR_ARG with `op`, the entry point's name, in the message.
+template <typename F>
+inline int pg_dispatch_dtype(int dtype, const char* op, F&& f) {
+  if (dtype == PG_F32) return f(float{});
+  if (dtype == PG_BF16) return f(bf16_t{});
+  pg_set_error("%s: bad dtype %d", op, dtype);
+  return PG_ERR_ARG;
+}
+
 // Opt kernel `fn` (parenthesise template arguments) in to `bytes` of dynamic LDS on the
 // current device, once per (call site, device): the attribute is per device, and a failed set
 // is reported here with its reason instead of surfacing later as a bare launch error.

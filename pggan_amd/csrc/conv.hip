@@ -66,25 +66,55 @@ struct ConvParams {
   const float* rb;    // toRGB bias [3]
 };
 
-// the RGBW operands of the next conv_hr launch on this host thread (pg_conv3x3_rgbw)
-struct RgbwArgs {
-  const float* img = nullptr;
-  float* dw = nullptr;
-  float* db = nullptr;
+// The operands of one conv launch, passed from the entry point down to the launcher that
+// fills ConvParams.  The RGB-epilogue operands (named as in ConvParams) are set only by
+// pg_conv3x3_rgbw / _rgbd / _rgbo.
+struct ConvArgs {
+  const void* x = nullptr;
+  const void* xbits = nullptr;
+  const void* wpk = nullptr;
+  const float* bias = nullptr;
+  const void* aux = nullptr;
+  void* y = nullptr;
+  void* y2 = nullptr;
+  void* ws = nullptr;
+  size_t ws_bytes = 0;
+  const float* rimg = nullptr;
+  float* rdw = nullptr;
+  float* rdb = nullptr;
   float* scratch = nullptr;
-  float s = 0.f;
-  // RGBD
+  float rscale = 0.f;
   const float* rw = nullptr;
+  const float* rb = nullptr;
   float* gimg = nullptr;
   float* norms = nullptr;
-  float f = 0.f;
-  // RGBO (rw, gimg, f as above)
-  const float* rb = nullptr;
+  float f2 = 0.f;
 };
-static thread_local RgbwArgs g_rgbw;
 
 int cinp_of(int c) { return c <= 16 ? ((c + 7) & ~7) : ((c + 31) & ~31); }
 __device__ __forceinline__ int cinp_of_dev(int c) { return c <= 16 ? ((c + 7) & ~7) : ((c + 31) & ~31); }
+
+// The ConvParams fields every launcher shares (shape, strides, flags, operands); the launcher
+// adds its own tile geometry.
+ConvParams conv_params(const pg_conv_desc* d, const ConvArgs& a) {
+  ConvParams p{};
+  p.x = a.x; p.w = a.wpk; p.bias = a.bias; p.aux = a.aux; p.y = a.y; p.y2 = a.y2;
+  p.B = d->B; p.H = d->H; p.W = d->W;
+  const bool ups = (d->flags & PG_CONV_UPS_IN) != 0;
+  p.Hin = ups ? d->H / 2 : d->H;
+  p.Win = ups ? d->W / 2 : d->W;
+  p.cin_p = cinp_of(d->cin);
+  p.cout = d->cout;
+  p.cout_p = (d->cout + 15) & ~15;
+  p.x_cs = d->x_cs; p.y_cs = d->y_cs; p.aux_cs = d->aux_cs; p.y2_cs = d->y2_cs;
+  p.flags = d->flags; p.slope = d->slope; p.out_scale = d->out_scale;
+  p.xbits = reinterpret_cast<const unsigned char*>(a.xbits);
+  p.xb_cs = d->xb_cs;
+  p.xcd_remap = 1;   // XCD-band tile order (FETCH of the MFMA-bound convs 1.60 -> 1.47x)
+  p.rimg = a.rimg; p.rdw = a.rdw; p.rdb = a.rdb; p.scratch = a.scratch; p.rscale = a.rscale;
+  p.rw = a.rw; p.rb = a.rb; p.gimg = a.gimg; p.norms = a.norms; p.f2 = a.f2;
+  return p;
+}
 
 struct TileCfg {
   int BM, BN, NB, TH, TW;
@@ -1629,20 +1659,9 @@ size_t conv_ws_bytes(const pg_conv_desc* d) {
 
 template <typename T, int BM, int BN, int WM, int WN, int MAXV, bool TR, int CKC = 0, int TWC = 0,
           int THC = 0>
-int launch_conv(const pg_conv_desc* d, const void* x, const void* wpk, const float* bias,
-                const void* aux, void* y, void* y2, void* ws, size_t ws_bytes, hipStream_t st) {
+int launch_conv(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
   TileCfg tc = pick_tile(d->H, d->W, BM, BN);
-  ConvParams p;
-  p.x = x; p.w = wpk; p.bias = bias; p.aux = aux; p.y = y; p.y2 = y2;
-  p.B = d->B; p.H = d->H; p.W = d->W;
-  const bool ups = (d->flags & PG_CONV_UPS_IN) != 0;
-  p.Hin = ups ? d->H / 2 : d->H;
-  p.Win = ups ? d->W / 2 : d->W;
-  p.cin_p = cinp_of(d->cin);
-  p.cout = d->cout;
-  p.cout_p = (d->cout + 15) & ~15;
-  p.x_cs = d->x_cs; p.y_cs = d->y_cs; p.aux_cs = d->aux_cs; p.y2_cs = d->y2_cs;
-  p.flags = d->flags; p.slope = d->slope; p.out_scale = d->out_scale;
+  ConvParams p = conv_params(d, a);
   p.NB = tc.NB; p.TH = tc.TH; p.TW = tc.TW;
   p.tiles_x = d->W / tc.TW;
   p.tiles_y = d->H / tc.TH;
@@ -1672,11 +1691,10 @@ int launch_conv(const pg_conv_desc* d, const void* x, const void* wpk, const flo
   }
   int splits = 1;
   const size_t need = conv_ws_bytes(d);
-  if (need && ws && ws_bytes >= need) splits = conv_splits(d);
-  p.ws = splits > 1 ? (float*)ws : nullptr;
+  if (need && a.ws && a.ws_bytes >= need) splits = conv_splits(d);
+  p.ws = splits > 1 ? (float*)a.ws : nullptr;
   p.cps = pg_cdiv(p.nchunks, splits);
   p.slab = (size_t)d->B * d->H * d->W * p.cout_p;
-  p.xcd_remap = 1;
   dim3 grid(pg_cdiv(d->B, tc.NB) * p.tiles_x * p.tiles_y, p.cout_p / BN + (p.cout_p % BN ? 1 : 0),
             splits);
   PG_LDS_ATTR((conv3x3_kernel<T, BM, BN, WM, WN, MAXV, TR, CKC, TWC, THC>), 160 * 1024);
@@ -1711,13 +1729,12 @@ int conv_vectors_per_thread(const pg_conv_desc* d, int BM, int BN) {
 }
 
 template <typename T, int BM, int BN>
-int launch_tr(const pg_conv_desc* d, const void* x, const void* wpk, const float* bias,
-              const void* aux, void* y, void* y2, void* ws, size_t wsb, hipStream_t st) {
+int launch_tr(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
   // fewest staging registers that fit -> highest occupancy for the HBM-bound high-res convs
   const int v = conv_vectors_per_thread<T>(d, BM, BN);
-  if (v <= 4) return launch_conv<T, BM, BN, 4, 1, 4, true>(d, x, wpk, bias, aux, y, y2, ws, wsb, st);
-  if (v <= 8) return launch_conv<T, BM, BN, 4, 1, 8, true>(d, x, wpk, bias, aux, y, y2, ws, wsb, st);
-  return launch_conv<T, BM, BN, 4, 1, 12, true>(d, x, wpk, bias, aux, y, y2, ws, wsb, st);
+  if (v <= 4) return launch_conv<T, BM, BN, 4, 1, 4, true>(d, a, st);
+  if (v <= 8) return launch_conv<T, BM, BN, 4, 1, 8, true>(d, a, st);
+  return launch_conv<T, BM, BN, 4, 1, 12, true>(d, a, st);
 }
 
 #include "conv_hr.inc"
@@ -1777,14 +1794,12 @@ bool conv_supported(const pg_conv_desc* d, size_t wsb) {
 }
 
 template <typename T>
-int conv_dispatch(const pg_conv_desc* d, const void* x, const void* wpk, const float* bias,
-                  const void* aux, void* y, void* y2, void* ws, size_t wsb, hipStream_t st,
-                  const void* xbits = nullptr) {
-  PG_CHECK_ARG(conv_supported<T>(d, wsb), "conv3x3_fwd: flags 0x%x not supported for cout %d at %dx%d",
+int conv_dispatch(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
+  PG_CHECK_ARG(conv_supported<T>(d, a.ws_bytes), "conv3x3_fwd: flags 0x%x not supported for cout %d at %dx%d",
                d->flags, d->cout, d->H, d->W);
   if constexpr (sizeof(T) == 2) {
-    if (conv_lr_ok(d)) return conv_lr_dispatch(d, x, wpk, bias, aux, y, y2, st);
-    if (conv_hr_ok(d)) return conv_hr_dispatch(d, x, wpk, bias, aux, y, y2, xbits, st);
+    if (conv_lr_ok(d)) return conv_lr_dispatch(d, a, st);
+    if (conv_hr_ok(d)) return conv_hr_dispatch(d, a, st);
   }
   int BM, BN;
   conv_tile_for(d->cout, &BM, &BN, d->W);
@@ -1796,22 +1811,22 @@ int conv_dispatch(const pg_conv_desc* d, const void* x, const void* wpk, const f
         const TileCfg tc = pick_tile(d->H, d->W, 128, 64);
 #define PG_LC(tw, th)                                                                            \
   if (tc.TW == tw && tc.TH == th)                                                                \
-    return launch_conv<T, 128, 64, PG_C64_WM, 2, 16 * 2 / PG_C64_WM, false, 32, tw, th>(d, x, wpk, bias, aux, y, y2, ws, wsb, st);
+    return launch_conv<T, 128, 64, PG_C64_WM, 2, 16 * 2 / PG_C64_WM, false, 32, tw, th>(d, a, st);
         PG_LC(4, 4)
         PG_LC(8, 8)
         PG_LC(16, 8)
 #undef PG_LC
-        return launch_conv<T, 128, 64, 2, 2, 16, false, 32>(d, x, wpk, bias, aux, y, y2, ws, wsb, st);
+        return launch_conv<T, 128, 64, 2, 2, 16, false, 32>(d, a, st);
       }
     }
-    return launch_conv<T, 128, 64, 2, 2, 16, false>(d, x, wpk, bias, aux, y, y2, ws, wsb, st);
+    return launch_conv<T, 128, 64, 2, 2, 16, false>(d, a, st);
   }
   if (BN == 32) {
-    if (BM == 256) return launch_tr<T, 256, 32>(d, x, wpk, bias, aux, y, y2, ws, wsb, st);
-    return launch_tr<T, 128, 32>(d, x, wpk, bias, aux, y, y2, ws, wsb, st);
+    if (BM == 256) return launch_tr<T, 256, 32>(d, a, st);
+    return launch_tr<T, 128, 32>(d, a, st);
   }
-  if (BM == 256) return launch_tr<T, 256, 16>(d, x, wpk, bias, aux, y, y2, ws, wsb, st);
-  return launch_tr<T, 128, 16>(d, x, wpk, bias, aux, y, y2, ws, wsb, st);
+  if (BM == 256) return launch_tr<T, 256, 16>(d, a, st);
+  return launch_tr<T, 128, 16>(d, a, st);
 }
 
 }  // namespace
@@ -1836,13 +1851,13 @@ int pg_conv3x3_pack(int dtype, int mode, int cout, int cin, const float* w_oihw,
   }
   const size_t total = (size_t)rows * 9 * kin;
   const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == PG_F32)
-    PG_KLAUNCH(pack_kernel<float>, dim3(blocks), dim3(256), 0, st, mode, cout, cin, rows,
-                       kin, w_oihw, scale, (float*)wpk);
-  else
-    PG_KLAUNCH(pack_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, mode, cout, cin, rows,
-                       kin, w_oihw, scale, (bf16_t*)wpk);
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    PG_KLAUNCH(pack_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, mode, cout, cin,
+               rows, kin, w_oihw, scale, (T*)wpk);
+    return PG_OK;
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
@@ -1851,20 +1866,20 @@ int pg_conv3x3_pack_batch(int dtype, int n, const pg_pack_item* items, int max_t
                           void* stream) {
   PG_CHECK_ARG(items && n > 0 && n < 65536 && max_tiles > 0, "conv3x3_pack_batch: bad args");
   const dim3 grid(max_tiles, n);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == PG_F32)
-    PG_KLAUNCH(pack_batch_kernel<float>, grid, dim3(256), 0, st, items);
-  else
-    PG_KLAUNCH(pack_batch_kernel<bf16_t>, grid, dim3(256), 0, st, items);
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    PG_KLAUNCH(pack_batch_kernel<decltype(t)>, grid, dim3(256), 0, (hipStream_t)stream, items);
+    return PG_OK;
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
 
 size_t pg_conv3x3_workspace_size(const pg_conv_desc* d) { return d ? conv_ws_bytes(d) : 0; }
 
-int pg_conv3x3_fwd(int dtype, const pg_conv_desc* d, const void* x, const void* wpk,
-                   const float* bias, const void* aux, void* y, void* y2, void* ws,
-                   size_t ws_bytes, void* stream) {
+int pg_conv3x3_fwd(int dtype, const pg_conv_desc* d, const void* x, const void* xbits,
+                   const void* wpk, const float* bias, const void* aux, void* y, void* y2,
+                   void* ws, size_t ws_bytes, void* stream) {
   PG_CHECK_ARG(d && x && wpk && y, "conv3x3_fwd: null pointer");
   PG_CHECK_ARG(d->B > 0 && d->H >= 4 && d->W >= 4 && (d->H & (d->H - 1)) == 0 &&
                    (d->W & (d->W - 1)) == 0,
@@ -1886,22 +1901,16 @@ int pg_conv3x3_fwd(int dtype, const pg_conv_desc* d, const void* x, const void* 
                "conv3x3_fwd: y2 only with POOL, PIXNORM, PNBWD or Y2_BITS");
   PG_CHECK_ARG(!(d->flags & PG_CONV_PNBWD) || (aux && y2 && d->aux_cs >= d->cout && d->aux_cs % 4 == 0),
                "conv3x3_fwd: PNBWD needs aux = y (aux_cs >= cout) and y2 = r");
-  PG_CHECK_ARG(dtype == PG_F32 || dtype == PG_BF16, "conv3x3_fwd: bad dtype");
-  PG_CHECK_ARG(!(d->flags & PG_CONV_X_BITS), "conv3x3_fwd: X_BITS needs pg_conv3x3_fwd_ex");
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == PG_F32) return conv_dispatch<float>(d, x, wpk, bias, aux, y, y2, ws, ws_bytes, st);
-  return conv_dispatch<bf16_t>(d, x, wpk, bias, aux, y, y2, ws, ws_bytes, st);
-}
-
-int pg_conv3x3_fwd_ex(int dtype, const pg_conv_desc* d, const void* x, const void* xbits,
-                      const void* wpk, const float* bias, const void* aux, void* y, void* y2,
-                      void* ws, size_t ws_bytes, void* stream) {
-  if (!d || !(d->flags & PG_CONV_X_BITS))
-    return pg_conv3x3_fwd(dtype, d, x, wpk, bias, aux, y, y2, ws, ws_bytes, stream);
-  PG_CHECK_ARG(xbits && dtype == PG_BF16, "conv3x3_fwd_ex: X_BITS needs xbits (bf16)");
-  PG_CHECK_ARG(x && wpk && y && d->cout % 4 == 0 && d->x_cs % 8 == 0 && d->y_cs >= d->cout,
-               "conv3x3_fwd_ex: bad args");
-  return conv_dispatch<bf16_t>(d, x, wpk, bias, aux, y, y2, ws, ws_bytes, (hipStream_t)stream, xbits);
+  PG_CHECK_ARG(!(d->flags & PG_CONV_X_BITS) || (xbits && dtype == PG_BF16),
+               "conv3x3_fwd: X_BITS needs xbits (bf16)");
+  PG_CHECK_ARG(!(d->flags & (PG_CONV_RGBW | PG_CONV_RGBD | PG_CONV_RGBO)),
+               "conv3x3_fwd: RGBW / RGBD / RGBO only through pg_conv3x3_rgbw / _rgbd / _rgbo");
+  ConvArgs a;
+  a.x = x; a.xbits = xbits; a.wpk = wpk; a.bias = bias; a.aux = aux; a.y = y; a.y2 = y2;
+  a.ws = ws; a.ws_bytes = ws_bytes;
+  return pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    return conv_dispatch<decltype(t)>(d, a, (hipStream_t)stream);
+  });
 }
 
 int pg_conv3x3_rgbw(int dtype, const pg_conv_desc* d, const void* x, const void* wpk,
@@ -1914,11 +1923,10 @@ int pg_conv3x3_rgbw(int dtype, const pg_conv_desc* d, const void* x, const void*
   PG_CHECK_ARG(d->x_cs >= cinp_of(d->cin) && d->x_cs % 8 == 0 && d->aux_cs * 8 >= d->cout,
                "conv3x3_rgbw: bad channel strides");
   PG_CHECK_ARG(pg_det_fits((size_t)256 * 8, (size_t)d->cout * 4), "conv3x3_rgbw: scratch too small");
-  g_rgbw.img = img; g_rgbw.dw = dw; g_rgbw.db = db; g_rgbw.scratch = (float*)scratch; g_rgbw.s = s;
-  const int rc = conv_dispatch<bf16_t>(d, x, wpk, nullptr, aux, nullptr, nullptr, nullptr, 0,
-                                       (hipStream_t)stream);
-  g_rgbw = RgbwArgs{};
-  return rc;
+  ConvArgs a;
+  a.x = x; a.wpk = wpk; a.aux = aux;
+  a.rimg = img; a.rdw = dw; a.rdb = db; a.scratch = (float*)scratch; a.rscale = s;
+  return conv_dispatch<bf16_t>(d, a, (hipStream_t)stream);
 }
 
 int pg_conv3x3_rgbd(int dtype, const pg_conv_desc* d, const void* x, const void* wpk,
@@ -1931,13 +1939,11 @@ int pg_conv3x3_rgbd(int dtype, const pg_conv_desc* d, const void* x, const void*
   PG_CHECK_ARG(d->x_cs >= cinp_of(d->cin) && d->x_cs % 8 == 0 && d->aux_cs * 8 >= d->cout,
                "conv3x3_rgbd: bad channel strides");
   PG_CHECK_ARG(pg_det_fits((size_t)256 * 8, (size_t)16 + d->cout * 4), "conv3x3_rgbd: scratch too small");
-  g_rgbw = RgbwArgs{};
-  g_rgbw.rw = w_rgb; g_rgbw.f = f; g_rgbw.gimg = gimg; g_rgbw.norms = norms; g_rgbw.dw = dw;
-  g_rgbw.s = s; g_rgbw.scratch = (float*)scratch;
-  const int rc = conv_dispatch<bf16_t>(d, x, wpk, nullptr, aux, nullptr, nullptr, nullptr, 0,
-                                       (hipStream_t)stream);
-  g_rgbw = RgbwArgs{};
-  return rc;
+  ConvArgs a;
+  a.x = x; a.wpk = wpk; a.aux = aux;
+  a.rw = w_rgb; a.f2 = f; a.gimg = gimg; a.norms = norms; a.rdw = dw; a.rscale = s;
+  a.scratch = (float*)scratch;
+  return conv_dispatch<bf16_t>(d, a, (hipStream_t)stream);
 }
 
 int pg_conv3x3_rgbo(int dtype, const pg_conv_desc* d, const void* x, const void* wpk,
@@ -1949,12 +1955,10 @@ int pg_conv3x3_rgbo(int dtype, const pg_conv_desc* d, const void* x, const void*
                d->cout, d->H, d->W);
   PG_CHECK_ARG(d->x_cs >= cinp_of(d->cin) && d->x_cs % 8 == 0 && d->y_cs >= d->cout,
                "conv3x3_rgbo: bad channel strides");
-  g_rgbw = RgbwArgs{};
-  g_rgbw.rw = w_rgb; g_rgbw.rb = b_rgb; g_rgbw.f = c; g_rgbw.gimg = img;
-  const int rc = conv_dispatch<bf16_t>(d, x, wpk, bias, nullptr, y, y2, nullptr, 0,
-                                       (hipStream_t)stream);
-  g_rgbw = RgbwArgs{};
-  return rc;
+  ConvArgs a;
+  a.x = x; a.wpk = wpk; a.bias = bias; a.y = y; a.y2 = y2;
+  a.rw = w_rgb; a.rb = b_rgb; a.f2 = c; a.gimg = img;
+  return conv_dispatch<bf16_t>(d, a, (hipStream_t)stream);
 }
 
 int pg_conv3x3_supported(int dtype, const pg_conv_desc* d, size_t ws_bytes) {
@@ -1968,13 +1972,17 @@ size_t pg_conv3x3_wgrad_workspace_size(int dtype, const pg_conv_desc* d) {
   return dtype == PG_BF16 ? wgrad_bf16_ws_bytes(d) : wgrad_f32_ws_bytes(d);
 }
 
-int pg_conv3x3_wgrad(int dtype, const pg_conv_desc* d, const void* x, const void* gz, float scale,
-                     float* dw, float* db, void* ws, size_t ws_bytes, void* stream) {
+int pg_conv3x3_wgrad(int dtype, const pg_conv_desc* d, const void* x, const void* gz,
+                     const void* gzbits, float scale, float* dw, float* db, void* ws,
+                     size_t ws_bytes, void* stream) {
   PG_CHECK_ARG(d && x && gz && dw, "conv3x3_wgrad: null pointer");
   PG_CHECK_ARG(d->B > 0 && d->H >= 4 && d->W >= 4, "conv3x3_wgrad: bad spatial size");
-  PG_CHECK_ARG(!(d->flags & PG_CONV_GZ_BITS), "conv3x3_wgrad: GZ_BITS needs pg_conv3x3_wgrad_ex");
+  const bool gzb = (d->flags & PG_CONV_GZ_BITS) != 0;
+  PG_CHECK_ARG(!gzb || (gzbits && dtype == PG_BF16), "conv3x3_wgrad: GZ_BITS needs gzbits (bf16)");
+  PG_CHECK_ARG(!gzb || (d->H % 2 == 0 && d->W % 2 == 0), "conv3x3_wgrad: GZ_BITS needs even H, W");
   if (dtype == PG_BF16)
-    return wgrad_bf16_dispatch(d, x, gz, scale, dw, db, (float*)ws, ws_bytes, (hipStream_t)stream);
+    return wgrad_bf16_dispatch(d, x, gz, scale, dw, db, (float*)ws, ws_bytes, (hipStream_t)stream,
+                               gzb ? gzbits : nullptr);
   TileCfg tc = pick_tile(d->H, d->W, WG_BP, 32);
   WgParams p;
   p.x = x; p.gz = gz; p.dw = dw; p.db = db;
@@ -2001,26 +2009,15 @@ int pg_conv3x3_wgrad(int dtype, const pg_conv_desc* d, const void* x, const void
   const int lds = (WG_BP * WG_RS + tc.NB * (tc.TH + 2) * (tc.TW + 2) * WG_RS) * 4;
   hipStream_t st = (hipStream_t)stream;
   dim3 grid(ot, ct, splits);
-  if (dtype == PG_F32)
-    PG_KLAUNCH(wgrad3x3_kernel<float>, grid, dim3(256), lds, st, p);
-  else
-    PG_KLAUNCH(wgrad3x3_kernel<bf16_t>, grid, dim3(256), lds, st, p);
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    PG_KLAUNCH(wgrad3x3_kernel<decltype(t)>, grid, dim3(256), lds, st, p);
+    return PG_OK;
+  });
+  if (rc != PG_OK) return rc;
   if (p.ws)
     launch_slab_reduce(p.ws, p.slab, splits, d->cout * d->cin * 9, dw, db, scale, st);
   PG_LAUNCH_CHECK();
   return PG_OK;
-}
-
-int pg_conv3x3_wgrad_ex(int dtype, const pg_conv_desc* d, const void* x, const void* gz,
-                        const void* gzbits, float scale, float* dw, float* db, void* ws,
-                        size_t ws_bytes, void* stream) {
-  if (!d || !(d->flags & PG_CONV_GZ_BITS))
-    return pg_conv3x3_wgrad(dtype, d, x, gz, scale, dw, db, ws, ws_bytes, stream);
-  PG_CHECK_ARG(x && gz && gzbits && dw && dtype == PG_BF16, "conv3x3_wgrad_ex: GZ_BITS needs gzbits (bf16)");
-  PG_CHECK_ARG(d->B > 0 && d->H >= 4 && d->W >= 4 && d->H % 2 == 0 && d->W % 2 == 0,
-               "conv3x3_wgrad_ex: bad spatial size");
-  return wgrad_bf16_dispatch(d, x, gz, scale, dw, db, (float*)ws, ws_bytes, (hipStream_t)stream,
-                             gzbits);
 }
 
 int pg_bias_grad(int dtype, int npix, int C, int cs, const void* g, float scale, float* db,
@@ -2036,13 +2033,13 @@ int pg_bias_grad(int dtype, int npix, int C, int cs, const void* g, float scale,
     ppb = pg_cdiv(npix, blocks);
     blocks = pg_cdiv(npix, ppb);
   }
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == PG_F32)
-    PG_KLAUNCH(bias_grad_kernel<float>, dim3(blocks), dim3(256), 0, st, npix, C, cs,
-                       (const float*)g, scale, db, ppb, (float*)scratch);
-  else
-    PG_KLAUNCH(bias_grad_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, npix, C, cs,
-                       (const bf16_t*)g, scale, db, ppb, (float*)scratch);
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    PG_KLAUNCH(bias_grad_kernel<T>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, npix, C, cs,
+               (const T*)g, scale, db, ppb, (float*)scratch);
+    return PG_OK;
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }

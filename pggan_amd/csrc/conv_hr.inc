@@ -1733,8 +1733,7 @@ int conv_hr_bn(const pg_conv_desc* d) {
 
 template <int CK, int TH, int BN, bool PERSIST, int NWAVES = 4, int MODE = HR_PLAIN, int PD = 1,
           bool DB = false, bool DMA = false, int EF = -1>
-int launch_conv_hr(const pg_conv_desc* d, const void* x, const void* wpk, const float* bias,
-                   const void* aux, void* y, void* y2, const void* xbits, hipStream_t st) {
+int launch_conv_hr(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
   constexpr int KS = (9 * CK + 31) / 32;
   constexpr int PIXB = CK * 2 + (CK * 2 >= 64 ? 32 : 0);
   constexpr int HALO_BYTES = ((TH + 2) * 18 * PIXB + 15) & ~15;
@@ -1745,39 +1744,17 @@ int launch_conv_hr(const pg_conv_desc* d, const void* x, const void* wpk, const 
                                 ((MODE == HR_XB || MODE == HR_XAB) ? 4096 : 0) +   // X_BITS select masks
                                 ((EF >= 0 && (EF & PG_CONV_RGBD)) ? NWAVES * 16 * 4 : 0);   // RGBD norms
   static_assert(LDS <= 160 * 1024, "conv_hr: LDS");
-  ConvParams p{};
-  p.x = x; p.w = wpk; p.bias = bias; p.aux = aux; p.y = y; p.y2 = y2;
-  p.B = d->B; p.H = d->H; p.W = d->W;
+  ConvParams p = conv_params(d, a);
   const bool ups = (d->flags & PG_CONV_UPS_IN) != 0;
-  p.Hin = ups ? d->H / 2 : d->H;
-  p.Win = ups ? d->W / 2 : d->W;
-  p.cin_p = cinp_of(d->cin);
-  p.cout = d->cout;
-  p.cout_p = (d->cout + 15) & ~15;
-  p.x_cs = d->x_cs; p.y_cs = d->y_cs; p.aux_cs = d->aux_cs; p.y2_cs = d->y2_cs;
-  p.flags = d->flags; p.slope = d->slope; p.out_scale = d->out_scale;
-  p.xbits = reinterpret_cast<const unsigned char*>(xbits);
-  p.xb_cs = d->xb_cs;
-  p.diag = 0;
-  p.xcd_remap = 1;   // XCD-band tile order (FETCH of the MFMA-bound convs 1.60 -> 1.47x)
-  if (d->flags & PG_CONV_RGBW) {
-    PG_CHECK_ARG(EF >= 0 && (EF & PG_CONV_RGBW) && g_rgbw.img && g_rgbw.dw && g_rgbw.scratch,
-                 "conv_hr: RGBW needs its EF variant and pg_conv3x3_rgbw's operands");
-    p.rimg = g_rgbw.img; p.rdw = g_rgbw.dw; p.rdb = g_rgbw.db; p.scratch = g_rgbw.scratch;
-    p.rscale = g_rgbw.s;
-  }
-  if (d->flags & PG_CONV_RGBO) {
-    PG_CHECK_ARG(EF >= 0 && (EF & PG_CONV_RGBO) && g_rgbw.rw && g_rgbw.rb && g_rgbw.gimg,
-                 "conv_hr: RGBO needs its EF variant and pg_conv3x3_rgbo's operands");
-    p.rw = g_rgbw.rw; p.rb = g_rgbw.rb; p.gimg = g_rgbw.gimg; p.f2 = g_rgbw.f;
-  }
-  if (d->flags & PG_CONV_RGBD) {
-    PG_CHECK_ARG(EF >= 0 && (EF & PG_CONV_RGBD) && g_rgbw.rw && g_rgbw.gimg && g_rgbw.scratch &&
-                     d->B <= 16,
-                 "conv_hr: RGBD needs its EF variant, pg_conv3x3_rgbd's operands and B <= 16");
-    p.rw = g_rgbw.rw; p.gimg = g_rgbw.gimg; p.norms = g_rgbw.norms; p.rdw = g_rgbw.dw;
-    p.scratch = g_rgbw.scratch; p.rscale = g_rgbw.s; p.f2 = g_rgbw.f;
-  }
+  PG_CHECK_ARG(!(d->flags & PG_CONV_RGBW) ||
+                   (EF >= 0 && (EF & PG_CONV_RGBW) && a.rimg && a.rdw && a.scratch),
+               "conv_hr: RGBW needs its EF variant and pg_conv3x3_rgbw's operands");
+  PG_CHECK_ARG(!(d->flags & PG_CONV_RGBO) ||
+                   (EF >= 0 && (EF & PG_CONV_RGBO) && a.rw && a.rb && a.gimg),
+               "conv_hr: RGBO needs its EF variant and pg_conv3x3_rgbo's operands");
+  PG_CHECK_ARG(!(d->flags & PG_CONV_RGBD) ||
+                   (EF >= 0 && (EF & PG_CONV_RGBD) && a.rw && a.gimg && a.scratch && d->B <= 16),
+               "conv_hr: RGBD needs its EF variant, pg_conv3x3_rgbd's operands and B <= 16");
   PG_CHECK_ARG((d->W / 16 & (d->W / 16 - 1)) == 0 && ((d->H / TH) & (d->H / TH - 1)) == 0,
                "conv_hr: tile counts must be powers of two");
   p.lg_tx = 0;
@@ -1785,10 +1762,10 @@ int launch_conv_hr(const pg_conv_desc* d, const void* x, const void* wpk, const 
   p.lg_ty = 0;
   while ((1 << p.lg_ty) < d->H / TH) ++p.lg_ty;
   PG_CHECK_ARG(d->H % TH == 0 && p.cin_p % CK == 0, "conv_hr: bad geometry");
-  PG_CHECK_ARG(!(d->flags & PG_CONV_X_BITS) || (xbits && d->xb_cs * 8 >= p.cin_p && ups),
+  PG_CHECK_ARG(!(d->flags & PG_CONV_X_BITS) || (a.xbits && d->xb_cs * 8 >= p.cin_p && ups),
                "conv_hr: X_BITS needs UPS_IN and xbits with >= cin/8 bytes per pixel");
   PG_CHECK_ARG(!PERSIST || (p.cin_p == CK && p.cout_p <= BN), "conv_hr: persist needs one chunk");
-  PG_CHECK_ARG(EF < 0 || ((d->flags | (y2 ? HR_EF_Y2 : 0)) == EF && d->cout == BN),
+  PG_CHECK_ARG(EF < 0 || ((d->flags | (a.y2 ? HR_EF_Y2 : 0)) == EF && d->cout == BN),
                "conv_hr: EF variant %d does not match flags %d / cout %d", EF, d->flags, d->cout);
   {  // the kernel addresses inside one image with 32-bit element offsets
     const size_t hw = (size_t)d->H * d->W;
@@ -1924,9 +1901,8 @@ bool conv_hr_mode_ok(const pg_conv_desc* d) {
 // ring depth 1 for the runtime-flag persistent variants (the round-1 sweep measured depth 1
 // fastest: deeper rings cost occupancy)
 template <int CK, int TH, int BN, bool PERSIST, int NW, int MODE>
-int launch_hr_pd(const pg_conv_desc* d, const void* x, const void* wpk, const float* bias,
-                 const void* aux, void* y, void* y2, const void* xbits, hipStream_t st) {
-  return launch_conv_hr<CK, TH, BN, PERSIST, NW, MODE, 1>(d, x, wpk, bias, aux, y, y2, xbits, st);
+int launch_hr_pd(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
+  return launch_conv_hr<CK, TH, BN, PERSIST, NW, MODE, 1>(d, a, st);
 }
 
 // waves of tile 3 (plain mode): 16 (2 x 4 blocks per wave, four waves per SIMD, 64 VGPRs)
@@ -1964,11 +1940,10 @@ int launch_hr_pd(const pg_conv_desc* d, const void* x, const void* wpk, const fl
 #define PG_HR_EF_PD 2
 #endif
 template <int CK, int TH, int BN, int MODE, int EF, int NW = 4>
-int launch_hr_ef(const pg_conv_desc* d, const void* x, const void* wpk, const float* bias,
-                 const void* aux, void* y, void* y2, const void* xbits, hipStream_t st) {
+int launch_hr_ef(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
   if constexpr (NW != 4) {
     constexpr int PDv = ((CK == 32 && BN == 16) || (CK == 16 && BN == 32)) ? 1 : PG_HR_EF_PD;
-    return launch_conv_hr<CK, TH, BN, true, NW, MODE, PDv, false, false, EF>(d, x, wpk, bias, aux, y, y2, xbits, st);
+    return launch_conv_hr<CK, TH, BN, true, NW, MODE, PDv, false, false, EF>(d, a, st);
   }
   // ring depth 2 by default: with depth 1 the loop entry (the first halo the youngest load)
   // and the back edge (the previous tile's stores younger than it) disagree, and the
@@ -1977,22 +1952,20 @@ int launch_hr_ef(const pg_conv_desc* d, const void* x, const void* wpk, const fl
   // (kbench: depth 1 is still faster for the 16 -> 32 pooled and 32 -> 16 tiles, 116 -> 64 /
   // 92 -> 87 us vs 79 / 95 at depth 2: their larger epilogue covers the halo latency)
   if ((CK == 32 && BN == 16) || (CK == 16 && BN == 32))
-    return launch_conv_hr<CK, TH, BN, true, 4, MODE, 1, false, false, EF>(d, x, wpk, bias, aux, y, y2, xbits, st);
-  return launch_conv_hr<CK, TH, BN, true, 4, MODE, PG_HR_EF_PD, false, false, EF>(d, x, wpk, bias, aux, y, y2, xbits, st);
+    return launch_conv_hr<CK, TH, BN, true, 4, MODE, 1, false, false, EF>(d, a, st);
+  return launch_conv_hr<CK, TH, BN, true, 4, MODE, PG_HR_EF_PD, false, false, EF>(d, a, st);
 }
 
 // The persistent narrow launches of the training step with their flags fixed at compile
 // time (EF, see conv_hr_kernel): (tile, mode, flags | HR_EF_Y2 if y2) as the engine issues
 // them at 512^2 / 1024^2.  Returns PG_ERR_UNSUPPORTED for anything else (runtime-flag form).
-int conv_hr_ef_dispatch(int tile, int m, const pg_conv_desc* d, const void* x, const void* wpk,
-                        const float* bias, const void* aux, void* y, void* y2, const void* xbits,
-                        hipStream_t st) {
-  const int ef = d->flags | (y2 ? HR_EF_Y2 : 0);
+int conv_hr_ef_dispatch(int tile, int m, const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
+  const int ef = d->flags | (a.y2 ? HR_EF_Y2 : 0);
   constexpr int Y = HR_EF_Y2;
   constexpr int PN = PG_CONV_PIXNORM | PG_CONV_LRELU | PG_CONV_BIAS;
-#define PG_HRX(T, MODE_, EFV, CK, TH, BN, ...)                                             \
-  if (tile == T && m == MODE_ && ef == (EFV) && d->cout == BN)                             \
-    return launch_hr_ef<CK, TH, BN, MODE_, (EFV), ##__VA_ARGS__>(d, x, wpk, bias, aux, y, y2, xbits, st);
+#define PG_HRX(T, MODE_, EFV, CK, TH, BN, ...)                      \
+  if (tile == T && m == MODE_ && ef == (EFV) && d->cout == BN)      \
+    return launch_hr_ef<CK, TH, BN, MODE_, (EFV), ##__VA_ARGS__>(d, a, st);
   // tile 0: 16 -> 16 (1024^2: D conv a fwd / dgrad / tangent, G conv b fwd / dgrad)
   PG_HRX(0, HR_PLAIN, 0, 16, 16, 16, PG_EF_NW)
   PG_HRX(0, HR_PLAIN, PG_CONV_LRELU | PG_CONV_BIAS, 16, 16, 16, PG_EF_NW)
@@ -2053,45 +2026,40 @@ int conv_hr_ef_dispatch(int tile, int m, const pg_conv_desc* d, const void* x, c
   return PG_ERR_UNSUPPORTED;
 }
 
-int conv_hr_dispatch(const pg_conv_desc* d, const void* x, const void* wpk, const float* bias,
-                     const void* aux, void* y, void* y2, const void* xbits, hipStream_t st) {
+int conv_hr_dispatch(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
   const int m = conv_hr_mode(d);
   PG_CHECK_ARG(conv_hr_mode_ok(d), "conv_hr: sign-bit mode %d not instantiated for this tile", m);
-#define PG_HR(T, ...)                                                                    \
-  case T:                                                                                \
-    if constexpr (T == 4 || T == 8 || T == 5) {                                          \
-      if (m == HR_XB)                                                                    \
-        return launch_hr_pd<__VA_ARGS__, HR_XB>(d, x, wpk, bias, aux, y, y2, xbits, st);  \
-      if (m == HR_XAB)                                                                   \
-        return launch_hr_pd<__VA_ARGS__, HR_XAB>(d, x, wpk, bias, aux, y, y2, xbits, st); \
-    }                                                                                    \
-    if constexpr (T == 1 || T == 3) {                                                    \
-      if (m == HR_YB)                                                                    \
-        return launch_hr_pd<__VA_ARGS__, HR_YB>(d, x, wpk, bias, aux, y, y2, xbits, st);  \
-      if (m == HR_AB)                                                                    \
-        return launch_hr_pd<__VA_ARGS__, HR_AB>(d, x, wpk, bias, aux, y, y2, xbits, st);  \
-    }                                                                                    \
-    return launch_hr_pd<__VA_ARGS__, HR_PLAIN>(d, x, wpk, bias, aux, y, y2, xbits, st);
+#define PG_HR(T, ...)                                                       \
+  case T:                                                                   \
+    if constexpr (T == 4 || T == 8 || T == 5) {                             \
+      if (m == HR_XB) return launch_hr_pd<__VA_ARGS__, HR_XB>(d, a, st);    \
+      if (m == HR_XAB) return launch_hr_pd<__VA_ARGS__, HR_XAB>(d, a, st);  \
+    }                                                                       \
+    if constexpr (T == 1 || T == 3) {                                       \
+      if (m == HR_YB) return launch_hr_pd<__VA_ARGS__, HR_YB>(d, a, st);    \
+      if (m == HR_AB) return launch_hr_pd<__VA_ARGS__, HR_AB>(d, a, st);    \
+    }                                                                       \
+    return launch_hr_pd<__VA_ARGS__, HR_PLAIN>(d, a, st);
   const int tile = conv_hr_tile(d);
   // tiles 3 (32 x 16 pixels x 64 channels, 8 waves) and 6 (16 x 16 x 64, 4 waves) with
   // LDS-DMA double-buffered staging
   if (tile == 6 && m == HR_PLAIN && cinp_of(d->cin) % 32 == 0) {
     if (PG_T6_NW == 8)   // the 8-wave asm-DMA form of tile 3 on 16-row tiles (two waves per SIMD)
-      return launch_conv_hr<32, 16, 64, false, 8, HR_PLAIN, 1, true, true>(d, x, wpk, bias, aux, y, y2, xbits, st);
-    return launch_conv_hr<32, 16, 64, false, 4, HR_PLAIN, 1, false, true>(d, x, wpk, bias, aux, y, y2, xbits, st);
+      return launch_conv_hr<32, 16, 64, false, 8, HR_PLAIN, 1, true, true>(d, a, st);
+    return launch_conv_hr<32, 16, 64, false, 4, HR_PLAIN, 1, false, true>(d, a, st);
   }
   if (tile == 13)   // conv_hr_t13 checked the mode (plain) and the geometry; two LDS slots
-    return launch_conv_hr<32, 8, 64, false, 4, HR_PLAIN, 1, false, true>(d, x, wpk, bias, aux, y, y2, xbits, st);
+    return launch_conv_hr<32, 8, 64, false, 4, HR_PLAIN, 1, false, true>(d, a, st);
   if (tile == 3 && cinp_of(d->cin) % 32 == 0) {
     // the inline-asm DMA form (overlapped staging, masks after the loop): A/B 298.0 -> 305.3
     // img/s, 5-7 % per launch
-    if (m == HR_YB) return launch_conv_hr<32, 32, 64, false, PG_T3B_NW, HR_YB, 1, true, true>(d, x, wpk, bias, aux, y, y2, xbits, st);
-    if (m == HR_AB) return launch_conv_hr<32, 32, 64, false, PG_T3B_NW, HR_AB, 1, true, true>(d, x, wpk, bias, aux, y, y2, xbits, st);
+    if (m == HR_YB) return launch_conv_hr<32, 32, 64, false, PG_T3B_NW, HR_YB, 1, true, true>(d, a, st);
+    if (m == HR_AB) return launch_conv_hr<32, 32, 64, false, PG_T3B_NW, HR_AB, 1, true, true>(d, a, st);
     if (m == HR_PLAIN)
-      return launch_conv_hr<32, 32, 64, false, PG_T3_NW, HR_PLAIN, 1, true, true>(d, x, wpk, bias, aux, y, y2, xbits, st);
+      return launch_conv_hr<32, 32, 64, false, PG_T3_NW, HR_PLAIN, 1, true, true>(d, a, st);
   }
   if (tile == 0 || tile == 1 || tile == 4 || tile == 5 || tile == 14 || tile == 15 || tile == 16) {
-    const int rc = conv_hr_ef_dispatch(tile, m, d, x, wpk, bias, aux, y, y2, xbits, st);
+    const int rc = conv_hr_ef_dispatch(tile, m, d, a, st);
     if (rc != PG_ERR_UNSUPPORTED) return rc;
     // tile 14's sign-bit modes and the unpooled YB / AB launches of tiles 0, 5 exist only as
     // the EF launches above

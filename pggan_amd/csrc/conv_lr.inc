@@ -235,20 +235,8 @@ bool conv_lr_ok(const pg_conv_desc* d) {
 }
 
 template <int W, int TH, int NCH>
-int launch_conv_lr(const pg_conv_desc* d, const void* x, const void* wpk, const float* bias,
-                   const void* aux, void* y, void* y2, hipStream_t st) {
-  ConvParams p{};
-  p.xcd_remap = 1;
-  p.x = x; p.w = wpk; p.bias = bias; p.aux = aux; p.y = y; p.y2 = y2;
-  p.B = d->B; p.H = d->H; p.W = d->W;
-  const bool ups = (d->flags & PG_CONV_UPS_IN) != 0;
-  p.Hin = ups ? d->H / 2 : d->H;
-  p.Win = ups ? d->W / 2 : d->W;
-  p.cin_p = cinp_of(d->cin);
-  p.cout = d->cout;
-  p.cout_p = (d->cout + 15) & ~15;
-  p.x_cs = d->x_cs; p.y_cs = d->y_cs; p.aux_cs = d->aux_cs; p.y2_cs = d->y2_cs;
-  p.flags = d->flags; p.slope = d->slope; p.out_scale = d->out_scale;
+int launch_conv_lr(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
+  const ConvParams p = conv_params(d, a);
   PG_CHECK_ARG(p.cin_p == NCH * 32 && d->H % TH == 0 && d->x_cs >= p.cin_p && (d->x_cs % 8) == 0,
                "conv_lr: bad geometry (H %d, x_cs %d, cin_p %d)", d->H, d->x_cs, p.cin_p);
   const int halo = (TH + 2) * (W + 2) * (p.cin_p * 2 + 32);
@@ -263,15 +251,14 @@ int launch_conv_lr(const pg_conv_desc* d, const void* x, const void* wpk, const 
 }
 
 template <int W, int TH>
-int conv_lr_nch(const pg_conv_desc* d, const void* x, const void* wpk, const float* bias,
-                const void* aux, void* y, void* y2, hipStream_t st) {
+int conv_lr_nch(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
   switch (cinp_of(d->cin) / 32) {
-    case 1: return launch_conv_lr<W, TH, 1>(d, x, wpk, bias, aux, y, y2, st);
-    case 2: return launch_conv_lr<W, TH, 2>(d, x, wpk, bias, aux, y, y2, st);
-    case 4: return launch_conv_lr<W, TH, 4>(d, x, wpk, bias, aux, y, y2, st);
-    case 8: return launch_conv_lr<W, TH, 8>(d, x, wpk, bias, aux, y, y2, st);
-    case 16: return launch_conv_lr<W, TH, 16>(d, x, wpk, bias, aux, y, y2, st);
-    case 17: return launch_conv_lr<W, TH, 17>(d, x, wpk, bias, aux, y, y2, st);
+    case 1: return launch_conv_lr<W, TH, 1>(d, a, st);
+    case 2: return launch_conv_lr<W, TH, 2>(d, a, st);
+    case 4: return launch_conv_lr<W, TH, 4>(d, a, st);
+    case 8: return launch_conv_lr<W, TH, 8>(d, a, st);
+    case 16: return launch_conv_lr<W, TH, 16>(d, a, st);
+    case 17: return launch_conv_lr<W, TH, 17>(d, a, st);
   }
   PG_CHECK_ARG(false, "conv_lr: no kernel for cin %d", d->cin);
   return PG_ERR_ARG;
@@ -282,16 +269,15 @@ bool conv_lr_nch_ok(int cin) {
   return cinp_of(cin) % 32 == 0 && (n == 1 || n == 2 || n == 4 || n == 8 || n == 16 || n == 17);
 }
 
-int conv_lr_dispatch(const pg_conv_desc* d, const void* x, const void* wpk, const float* bias,
-                     const void* aux, void* y, void* y2, hipStream_t st) {
+int conv_lr_dispatch(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
   switch (d->W) {
-    case 4: return conv_lr_nch<4, 4>(d, x, wpk, bias, aux, y, y2, st);
+    case 4: return conv_lr_nch<4, 4>(d, a, st);
     case 8:
       // whole-image tiles when that still gives 256 workgroups (the merged passes, B = 8):
       // each 16-channel weight slab is streamed by 8 workgroups instead of 16, 17.7 -> 14.0 us
       // per launch (profiles/r5_lowres_tiles.txt)
-      if (d->B >= 8) return conv_lr_nch<8, 8>(d, x, wpk, bias, aux, y, y2, st);
-      return conv_lr_nch<8, 4>(d, x, wpk, bias, aux, y, y2, st);
+      if (d->B >= 8) return conv_lr_nch<8, 8>(d, a, st);
+      return conv_lr_nch<8, 4>(d, a, st);
   }
   return PG_ERR_ARG;
 }

@@ -1079,15 +1079,6 @@ __global__ __launch_bounds__(256) void r1_kernel(int B, size_t n, const float* g
   det_commit_seg(t, 1, scratch, tmp, [&](int, float v) { r1[0] += 0.5f * v * inv; });
 }
 
-__global__ void gp_interp_kernel(int B, size_t per, const float* xr, const float* xf,
-                                 const float* eps, float* out) {
-  const size_t n = (size_t)B * per;
-  GRID_STRIDE(i, n) {
-    const float e = eps[i / per];
-    out[i] = e * xr[i] + (1.f - e) * xf[i];
-  }
-}
-
 // grid (gx, B): the blocks of sample b are the contiguous index range [b gx, (b + 1) gx)
 __global__ __launch_bounds__(256) void sumsq_per_sample_kernel(int B, size_t per, const float* g,
                                                                float* norms, float* scratch) {
@@ -1249,39 +1240,24 @@ __global__ void cast_kernel(size_t n, const A* x, B* y) {
 
 }  // namespace
 
-#define DT_DISPATCH(dtype, KERNEL, grid, block, shm, st, ...)                                  \
-  do {                                                                                         \
-    if ((dtype) == PG_F32)                                                                     \
-      PG_KLAUNCH(KERNEL<float>, grid, block, shm, st, __VA_ARGS__);                    \
-    else if ((dtype) == PG_BF16)                                                               \
-      PG_KLAUNCH(KERNEL<bf16_t>, grid, block, shm, st, __VA_ARGS__);                   \
-    else {                                                                                     \
-      pg_set_error("%s: bad dtype %d", __func__, (int)(dtype));                                \
-      return PG_ERR_ARG;                                                                       \
-    }                                                                                          \
-  } while (0)
-
 extern "C" {
 
 const char* pg_last_error(void) { return g_err; }
-int pg_version(void) { return 100; }
+int pg_version(void) { return 101; }
 
 int pg_pixnorm_fwd(int dtype, int npix, int C, int cs, const void* x, void* y, void* stream) {
   PG_CHECK_ARG(x && y && npix > 0 && C % 4 == 0 && cs >= C && cs % 4 == 0, "pixnorm_fwd: bad args");
   hipStream_t st = (hipStream_t)stream;
-  if ((dtype == PG_F32 ? try_pixnorm_fwd<float>(npix, C, cs, (const float*)x, (float*)y, st)
-                       : try_pixnorm_fwd<bf16_t>(npix, C, cs, (const bf16_t*)x, (bf16_t*)y, st)) == 0) {
-    PG_LAUNCH_CHECK();
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    if (try_pixnorm_fwd<T>(npix, C, cs, (const T*)x, (T*)y, st) == 0) return PG_OK;
+    const int L = lanes_for(C);
+    const size_t threads = (size_t)npix * L;
+    PG_KLAUNCH(pixnorm_fwd_kernel<T>, dim3((threads + 255) / 256), dim3(256), 0, st, npix, C, cs, L,
+               (const T*)x, (T*)y);
     return PG_OK;
-  }
-  const int L = lanes_for(C);
-  const size_t threads = (size_t)npix * L;
-  if (dtype == PG_F32)
-    PG_KLAUNCH(pixnorm_fwd_kernel<float>, dim3((threads + 255) / 256), dim3(256), 0, st,
-                       npix, C, cs, L, (const float*)x, (float*)y);
-  else
-    PG_KLAUNCH(pixnorm_fwd_kernel<bf16_t>, dim3((threads + 255) / 256), dim3(256), 0, st,
-                       npix, C, cs, L, (const bf16_t*)x, (bf16_t*)y);
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
@@ -1290,23 +1266,17 @@ int pg_pixnorm_lrelu_bwd(int dtype, int npix, int C, int cs, const void* u, cons
                          float slope, int apply_mask, void* gz, void* stream) {
   PG_CHECK_ARG(u && gy && gz && npix > 0 && C % 4 == 0 && cs >= C, "pixnorm_lrelu_bwd: bad args");
   hipStream_t st = (hipStream_t)stream;
-  if ((dtype == PG_F32 ? try_pixnorm_bwd<float>(npix, C, cs, (const float*)u, (const float*)gy, slope,
-                                                apply_mask, (float*)gz, st)
-                       : try_pixnorm_bwd<bf16_t>(npix, C, cs, (const bf16_t*)u, (const bf16_t*)gy,
-                                                 slope, apply_mask, (bf16_t*)gz, st)) == 0) {
-    PG_LAUNCH_CHECK();
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    if (try_pixnorm_bwd<T>(npix, C, cs, (const T*)u, (const T*)gy, slope, apply_mask, (T*)gz, st) == 0)
+      return PG_OK;
+    const int L = lanes_for(C);
+    const size_t threads = (size_t)npix * L;
+    PG_KLAUNCH(pixnorm_lrelu_bwd_kernel<T>, dim3((threads + 255) / 256), dim3(256), 0, st, npix, C,
+               cs, L, (const T*)u, (const T*)gy, slope, apply_mask, (T*)gz);
     return PG_OK;
-  }
-  const int L = lanes_for(C);
-  const size_t threads = (size_t)npix * L;
-  if (dtype == PG_F32)
-    PG_KLAUNCH(pixnorm_lrelu_bwd_kernel<float>, dim3((threads + 255) / 256), dim3(256), 0,
-                       st, npix, C, cs, L, (const float*)u, (const float*)gy, slope, apply_mask,
-                       (float*)gz);
-  else
-    PG_KLAUNCH(pixnorm_lrelu_bwd_kernel<bf16_t>, dim3((threads + 255) / 256), dim3(256), 0,
-                       st, npix, C, cs, L, (const bf16_t*)u, (const bf16_t*)gy, slope, apply_mask,
-                       (bf16_t*)gz);
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
@@ -1314,58 +1284,44 @@ int pg_pixnorm_lrelu_bwd(int dtype, int npix, int C, int cs, const void* u, cons
 int pg_pixnorm_lrelu_bwd_y(int dtype, int npix, int C, int cs, const void* y, const float* r,
                            const void* gy, float slope, void* gz, void* stream) {
   PG_CHECK_ARG(y && r && gy && gz && npix > 0 && C > 0 && cs >= C, "pixnorm_lrelu_bwd_y: bad args");
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = dtype == PG_F32
-                     ? try_pixnorm_bwd_y<float>(npix, C, cs, (const float*)y, r, (const float*)gy,
-                                                slope, (float*)gz, st)
-                     : try_pixnorm_bwd_y<bf16_t>(npix, C, cs, (const bf16_t*)y, r,
-                                                 (const bf16_t*)gy, slope, (bf16_t*)gz, st);
-  PG_CHECK_ARG(rc == 0, "pixnorm_lrelu_bwd_y: C=%d (stride %d) needs a power-of-two count of 16-byte vectors <= 64",
-               C, cs);
-  PG_LAUNCH_CHECK();
-  return PG_OK;
-}
-
-int pg_unpool_mask_bits(int dtype, int B, int H, int W, int C, int g_cs, const void* g,
-                        const void* bits, float scale, float slope, int ups, int out_cs, void* out,
-                        void* stream) {
-  PG_CHECK_ARG(dtype == PG_BF16 && g && bits && out && C % 8 == 0 &&
-                   (!ups || (H % 2 == 0 && W % 2 == 0)),
-               "unpool_mask_bits: bad args (bf16, C %% 8 == 0)");
-  if (try_unpool_mask<bf16_t>(B, H, W, C, g_cs, (const bf16_t*)g, 0, nullptr, scale, slope, ups,
-                              out_cs, (bf16_t*)out, (hipStream_t)stream,
-                              (const uint8_t*)bits) != 0) {
-    pg_set_error("unpool_mask_bits: unsupported layout (C %d, strides %d / %d)", C, g_cs, out_cs);
-    return PG_ERR_ARG;
-  }
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    PG_CHECK_ARG(try_pixnorm_bwd_y<T>(npix, C, cs, (const T*)y, r, (const T*)gy, slope, (T*)gz,
+                                      (hipStream_t)stream) == 0,
+                 "pixnorm_lrelu_bwd_y: C=%d (stride %d) needs a power-of-two count of 16-byte vectors <= 64",
+                 C, cs);
+    return PG_OK;
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
 
 int pg_unpool_mask(int dtype, int B, int H, int W, int C, int g_cs, const void* g, int y_cs,
-                   const void* y, float scale, float slope, int ups, int out_cs, void* out,
-                   void* stream) {
+                   const void* y, const void* bits, float scale, float slope, int ups, int out_cs,
+                   void* out, void* stream) {
   PG_CHECK_ARG(g && out && C % 4 == 0 && (!ups || (H % 2 == 0 && W % 2 == 0)),
                "unpool_mask: bad args");
-  const size_t n = (size_t)B * H * W * (C / 4);
+  PG_CHECK_ARG(!bits || (dtype == PG_BF16 && C % 8 == 0), "unpool_mask: bits need bf16, C %% 8 == 0");
   hipStream_t st = (hipStream_t)stream;
-  if ((dtype == PG_F32 ? try_unpool_mask<float>(B, H, W, C, g_cs, (const float*)g, y_cs,
-                                                (const float*)y, scale, slope, ups, out_cs,
-                                                (float*)out, st)
-                       : try_unpool_mask<bf16_t>(B, H, W, C, g_cs, (const bf16_t*)g, y_cs,
-                                                 (const bf16_t*)y, scale, slope, ups, out_cs,
-                                                 (bf16_t*)out, st)) == 0) {
-    PG_LAUNCH_CHECK();
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    if (bits) {   // the vector kernel only
+      PG_CHECK_ARG(try_unpool_mask<T>(B, H, W, C, g_cs, (const T*)g, 0, nullptr, scale, slope, ups,
+                                      out_cs, (T*)out, st, (const uint8_t*)bits) == 0,
+                   "unpool_mask: bits with an unsupported layout (C %d, strides %d / %d)", C, g_cs,
+                   out_cs);
+      return PG_OK;
+    }
+    if (try_unpool_mask<T>(B, H, W, C, g_cs, (const T*)g, y_cs, (const T*)y, scale, slope, ups,
+                           out_cs, (T*)out, st) == 0)
+      return PG_OK;
+    const size_t n = (size_t)B * H * W * (C / 4);
+    PG_KLAUNCH(unpool_mask_kernel<T>, dim3(grid_for(n)), dim3(256), 0, st, B, H, W, C, g_cs,
+               (const T*)g, y_cs, (const T*)y, scale, slope, ups, out_cs, (T*)out);
     return PG_OK;
-  }
-  if (dtype == PG_F32)
-    PG_KLAUNCH(unpool_mask_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, B, H, W, C,
-                       g_cs, (const float*)g, y_cs, (const float*)y, scale, slope, ups, out_cs,
-                       (float*)out);
-  else
-    PG_KLAUNCH(unpool_mask_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, st, B, H, W, C,
-                       g_cs, (const bf16_t*)g, y_cs, (const bf16_t*)y, scale, slope, ups, out_cs,
-                       (bf16_t*)out);
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
@@ -1373,20 +1329,16 @@ int pg_unpool_mask(int dtype, int B, int H, int W, int C, int g_cs, const void* 
 int pg_avgpool2(int dtype, int B, int H, int W, int C, int x_cs, const void* x, int y_cs, void* y,
                 void* stream) {
   PG_CHECK_ARG(x && y && C % 4 == 0 && H % 2 == 0 && W % 2 == 0, "avgpool2: bad args");
-  const size_t n = (size_t)B * (H / 2) * (W / 2) * (C / 4);
   hipStream_t st = (hipStream_t)stream;
-  if ((dtype == PG_F32 ? try_avgpool2<float>(B, H, W, C, x_cs, (const float*)x, y_cs, (float*)y, st)
-                       : try_avgpool2<bf16_t>(B, H, W, C, x_cs, (const bf16_t*)x, y_cs, (bf16_t*)y,
-                                              st)) == 0) {
-    PG_LAUNCH_CHECK();
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    if (try_avgpool2<T>(B, H, W, C, x_cs, (const T*)x, y_cs, (T*)y, st) == 0) return PG_OK;
+    const size_t n = (size_t)B * (H / 2) * (W / 2) * (C / 4);
+    PG_KLAUNCH(avgpool2_kernel<T>, dim3(grid_for(n)), dim3(256), 0, st, B, H, W, C, x_cs,
+               (const T*)x, y_cs, (T*)y);
     return PG_OK;
-  }
-  if (dtype == PG_F32)
-    PG_KLAUNCH(avgpool2_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, B, H, W, C,
-                       x_cs, (const float*)x, y_cs, (float*)y);
-  else
-    PG_KLAUNCH(avgpool2_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, st, B, H, W, C,
-                       x_cs, (const bf16_t*)x, y_cs, (bf16_t*)y);
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
@@ -1395,18 +1347,14 @@ int pg_blend(int dtype, size_t n, float a, const void* x, float b, const void* y
              void* stream) {
   PG_CHECK_ARG(x && out, "blend: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  if ((dtype == PG_F32 ? try_blend<float>(n, a, (const float*)x, b, (const float*)y, (float*)out, st)
-                       : try_blend<bf16_t>(n, a, (const bf16_t*)x, b, (const bf16_t*)y, (bf16_t*)out,
-                                           st)) == 0) {
-    PG_LAUNCH_CHECK();
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    if (try_blend<T>(n, a, (const T*)x, b, (const T*)y, (T*)out, st) == 0) return PG_OK;
+    PG_KLAUNCH(blend_kernel<T>, dim3(grid_for(n)), dim3(256), 0, st, n, a, (const T*)x, b,
+               (const T*)y, (T*)out);
     return PG_OK;
-  }
-  if (dtype == PG_F32)
-    PG_KLAUNCH(blend_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, n, a,
-                       (const float*)x, b, (const float*)y, (float*)out);
-  else
-    PG_KLAUNCH(blend_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, st, n, a,
-                       (const bf16_t*)x, b, (const bf16_t*)y, (bf16_t*)out);
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
@@ -1416,23 +1364,18 @@ int pg_rgb_out(int dtype, int B, int R, int C, int x_cs, const void* x, const fl
                const float* bp, float cp, float alpha, float* img, void* stream) {
   PG_CHECK_ARG(x && w && b && img && C % 4 == 0 && (!xp || (wp && bp && Cp % 4 == 0 && R % 2 == 0)),
                "rgb_out: bad args");
-  const size_t n = (size_t)B * R * R;
   hipStream_t st = (hipStream_t)stream;
-  if ((dtype == PG_F32
-           ? try_rgb_out<float>(B, R, C, x_cs, (const float*)x, w, b, c, Cp, xp_cs, (const float*)xp,
-                                wp, bp, cp, alpha, img, st)
-           : try_rgb_out<bf16_t>(B, R, C, x_cs, (const bf16_t*)x, w, b, c, Cp, xp_cs,
-                                 (const bf16_t*)xp, wp, bp, cp, alpha, img, st)) == 0) {
-    PG_LAUNCH_CHECK();
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    if (try_rgb_out<T>(B, R, C, x_cs, (const T*)x, w, b, c, Cp, xp_cs, (const T*)xp, wp, bp, cp,
+                       alpha, img, st) == 0)
+      return PG_OK;
+    const size_t n = (size_t)B * R * R;
+    PG_KLAUNCH(rgb_out_kernel<T>, dim3(grid_for(n)), dim3(256), 0, st, B, R, C, x_cs, (const T*)x,
+               w, b, c, Cp, xp_cs, (const T*)xp, wp, bp, cp, alpha, img);
     return PG_OK;
-  }
-  if (dtype == PG_F32)
-    PG_KLAUNCH(rgb_out_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, B, R, C, x_cs,
-                       (const float*)x, w, b, c, Cp, xp_cs, (const float*)xp, wp, bp, cp, alpha, img);
-  else
-    PG_KLAUNCH(rgb_out_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, st, B, R, C, x_cs,
-                       (const bf16_t*)x, w, b, c, Cp, xp_cs, (const bf16_t*)xp, wp, bp, cp, alpha,
-                       img);
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
@@ -1525,171 +1468,105 @@ int pg_rgb_out_bwd(int dtype, int B, int R, int C, int x_cs, const void* x, cons
                    float* dwp, float* dbp, void* scratch, void* stream) {
   PG_CHECK_ARG(x && w && gimg && C % 4 == 0 && (!xp || (wp && Cp % 4 == 0)), "rgb_out_bwd: bad args");
   PG_CHECK_ARG(scratch || !(dw || db || dwp || dbp), "rgb_out_bwd: weight gradients need scratch");
-  hipStream_t st = (hipStream_t)stream;
-  float* sc = (float*)scratch;
-  if (dtype == PG_F32)
-    return rgb_bwd_impl<float>(B, R, C, x_cs, (const float*)x, w, c, Cp, xp_cs, (const float*)xp,
-                               wp, cp, alpha, gimg, (float*)gx, (float*)gxp, dw, db, dwp, dbp, sc, st);
-  return rgb_bwd_impl<bf16_t>(B, R, C, x_cs, (const bf16_t*)x, w, c, Cp, xp_cs, (const bf16_t*)xp,
-                              wp, cp, alpha, gimg, (bf16_t*)gx, (bf16_t*)gxp, dw, db, dwp, dbp, sc, st);
+  return pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    return rgb_bwd_impl<T>(B, R, C, x_cs, (const T*)x, w, c, Cp, xp_cs, (const T*)xp, wp, cp, alpha,
+                           gimg, (T*)gx, (T*)gxp, dw, db, dwp, dbp, (float*)scratch,
+                           (hipStream_t)stream);
+  });
 }
 
 int pg_rgb_out_bwd_pn(int dtype, int B, int R, int C, int y_cs, const void* y, const float* r,
                       const float* w, float c, const float* gimg, float slope, int gz_cs, void* gz,
-                      void* stream) {
+                      float* dw, float* db, void* scratch, void* stream) {
   PG_CHECK_ARG(y && r && w && gimg && gz && (C == 16 || C == 32), "rgb_out_bwd_pn: bad args (C 16 / 32)");
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = dtype == PG_F32
-                     ? try_rgb_dgrad_pn<float>(B, R, C, y_cs, (const float*)y, r, w, c, slope, gimg, gz_cs,
-                                               (float*)gz, st)
-                     : try_rgb_dgrad_pn<bf16_t>(B, R, C, y_cs, (const bf16_t*)y, r, w, c, slope, gimg,
-                                                gz_cs, (bf16_t*)gz, st);
-  PG_CHECK_ARG(rc == 0, "rgb_out_bwd_pn: unsupported strides (%d, %d)", y_cs, gz_cs);
-  PG_LAUNCH_CHECK();
-  return PG_OK;
-}
-
-int pg_rgb_out_bwd_pn_wg(int dtype, int B, int R, int C, int y_cs, const void* y, const float* r,
-                         const float* w, float c, const float* gimg, float slope, int gz_cs,
-                         void* gz, float* dw, float* db, void* scratch, void* stream) {
-  PG_CHECK_ARG(y && r && w && gimg && gz && dw && scratch && (C == 16 || C == 32),
-               "rgb_out_bwd_pn_wg: bad args (C 16 / 32)");
-  hipStream_t st = (hipStream_t)stream;
-  const int rc = dtype == PG_F32
-                     ? try_rgb_dgrad_pn<float>(B, R, C, y_cs, (const float*)y, r, w, c, slope, gimg,
-                                               gz_cs, (float*)gz, st, dw, db, (float*)scratch)
-                     : try_rgb_dgrad_pn<bf16_t>(B, R, C, y_cs, (const bf16_t*)y, r, w, c, slope, gimg,
-                                                gz_cs, (bf16_t*)gz, st, dw, db, (float*)scratch);
-  PG_CHECK_ARG(rc == 0, "rgb_out_bwd_pn_wg: unsupported strides (%d, %d)", y_cs, gz_cs);
-  PG_LAUNCH_CHECK();
-  return PG_OK;
-}
-
-static int from_rgb_impl(int dtype, int B, int R, int C, const ImgSrc& img, int down,
-                         const float* w, const float* b, float c, float slope, const void* mask_y,
-                         int y_cs, void* y, hipStream_t st) {
-  PG_CHECK_ARG(img && w && y && C % 4 == 0 && y_cs >= C, "from_rgb: bad args");
-  const size_t n = (size_t)B * R * R * (C / 4);
-  if ((dtype == PG_F32 ? try_from_rgb<float>(B, R, C, img, down, w, b, c, slope, (const float*)mask_y,
-                                             y_cs, (float*)y, st)
-                       : try_from_rgb<bf16_t>(B, R, C, img, down, w, b, c, slope,
-                                              (const bf16_t*)mask_y, y_cs, (bf16_t*)y, st)) == 0) {
-    PG_LAUNCH_CHECK();
+  PG_CHECK_ARG(dw ? scratch != nullptr : !db,
+               "rgb_out_bwd_pn: dw needs scratch, db only with dw");
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    PG_CHECK_ARG(try_rgb_dgrad_pn<T>(B, R, C, y_cs, (const T*)y, r, w, c, slope, gimg, gz_cs, (T*)gz,
+                                     (hipStream_t)stream, dw, db, (float*)scratch) == 0,
+                 "rgb_out_bwd_pn: unsupported strides (%d, %d)", y_cs, gz_cs);
     return PG_OK;
-  }
-  if (dtype == PG_F32)
-    PG_KLAUNCH(from_rgb_kernel<float>, dim3(grid_for(n)), dim3(256), 0, st, B, R, C, img,
-                       down, w, b, c, slope, (const float*)mask_y, y_cs, (float*)y);
-  else
-    PG_KLAUNCH(from_rgb_kernel<bf16_t>, dim3(grid_for(n)), dim3(256), 0, st, B, R, C, img,
-                       down, w, b, c, slope, (const bf16_t*)mask_y, y_cs, (bf16_t*)y);
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
 
-int pg_from_rgb(int dtype, int B, int R, int C, const float* img, int down, const float* w,
-                const float* b, float c, float slope, const void* mask_y, int y_cs, void* y,
-                void* stream) {
-  return from_rgb_impl(dtype, B, R, C, ImgSrc(img), down, w, b, c, slope, mask_y, y_cs, y,
-                       (hipStream_t)stream);
+int pg_from_rgb(int dtype, int B, int R, int C, const pg_img_src* img, int down, const float* w,
+                const float* b, float c, float slope, const void* mask_y, const void* mask_bits,
+                int y_cs, void* y, void* ybits, void* stream) {
+  PG_CHECK_ARG(img && img->x0 && w && y && C % 4 == 0 && y_cs >= C, "from_rgb: bad args");
+  PG_CHECK_ARG(!img->x1 || (img->a && img->c), "from_rgb: bad image source");
+  PG_CHECK_ARG(!(mask_bits && ybits), "from_rgb: mask_bits (tangent) or ybits (forward)");
+  const bool bits = mask_bits || ybits;
+  PG_CHECK_ARG(!bits || (dtype == PG_BF16 && C % 8 == 0 && C <= 64 && !mask_y),
+               "from_rgb: bits need bf16, C %% 8 == 0, C <= 64 and no mask_y");
+  const ImgSrc src(*img);
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    const int vec = try_from_rgb<T>(B, R, C, src, down, w, b, c, slope, (const T*)mask_y, y_cs, (T*)y,
+                                    st, (const uint8_t*)mask_bits, (uint8_t*)ybits);
+    PG_CHECK_ARG(vec == 0 || !bits, "from_rgb: bits with an unsupported layout (y_cs %d)", y_cs);
+    if (vec == 0) return PG_OK;
+    const size_t n = (size_t)B * R * R * (C / 4);
+    PG_KLAUNCH(from_rgb_kernel<T>, dim3(grid_for(n)), dim3(256), 0, st, B, R, C, src, down, w, b, c,
+               slope, (const T*)mask_y, y_cs, (T*)y);
+    return PG_OK;
+  });
+  if (rc != PG_OK) return rc;
+  PG_LAUNCH_CHECK();
+  return PG_OK;
 }
 
-int pg_from_rgb_src(int dtype, int B, int R, int C, const pg_img_src* img, int down, const float* w,
-                    const float* b, float c, float slope, const void* mask_y, int y_cs, void* y,
+int pg_from_rgb_bwd(int dtype, int B, int R, int C, const pg_img_src* img, int down,
+                    const float* w, float c, int gz_cs, const void* gz, float* gimg,
+                    int gimg_overwrite, float* norms, float* dw, float* db, void* scratch,
                     void* stream) {
-  PG_CHECK_ARG(img && (!img->x1 || (img->a && img->c)), "from_rgb_src: bad image source");
-  return from_rgb_impl(dtype, B, R, C, ImgSrc(*img), down, w, b, c, slope, mask_y, y_cs, y,
-                       (hipStream_t)stream);
-}
-
-int pg_from_rgb_bits(int dtype, int B, int R, int C, const pg_img_src* img, int down,
-                     const float* w, const float* b, float c, float slope, const void* mask_bits,
-                     int y_cs, void* y, void* ybits, void* stream) {
-  PG_CHECK_ARG(dtype == PG_BF16 && img && w && y && C % 8 == 0 && C <= 64 && y_cs >= C &&
-                   (!img->x1 || (img->a && img->c)),
-               "from_rgb_bits: bad args (bf16, C %% 8 == 0, C <= 64)");
-  PG_CHECK_ARG(!(mask_bits && ybits), "from_rgb_bits: mask_bits (tangent) or ybits (forward)");
-  if (try_from_rgb<bf16_t>(B, R, C, ImgSrc(*img), down, w, b, c, slope, nullptr, y_cs, (bf16_t*)y,
-                           (hipStream_t)stream, (const uint8_t*)mask_bits, (uint8_t*)ybits) != 0) {
-    pg_set_error("from_rgb_bits: unsupported layout (y_cs %d)", y_cs);
-    return PG_ERR_ARG;
-  }
-  PG_LAUNCH_CHECK();
-  return PG_OK;
-}
-
-static int from_rgb_bwd_impl(int dtype, int B, int R, int C, const ImgSrc& img, int down,
-                             const float* w, float c, int gz_cs, const void* gz, float* gimg, int ow,
-                             float* norms, float* dw, float* db, float* scratch, hipStream_t st) {
+  PG_CHECK_ARG(!img || !img->x1 || (img->a && img->c), "from_rgb_bwd: bad image source");
   PG_CHECK_ARG(w && gz && C % 4 == 0, "from_rgb_bwd: bad args");
-  PG_CHECK_ARG(!(dw || db) || img, "from_rgb_bwd: wgrad needs img");
+  PG_CHECK_ARG(!(dw || db) || (img && img->x0), "from_rgb_bwd: wgrad needs img");
   PG_CHECK_ARG(!norms || gimg, "from_rgb_bwd: norms need gimg");
   PG_CHECK_ARG(scratch || !(dw || db || norms), "from_rgb_bwd: weight gradients / norms need scratch");
-  if ((dtype == PG_F32 ? try_from_rgb_bwd<float>(B, R, C, img, down, w, c, gz_cs, (const float*)gz,
-                                                 gimg, ow, norms, dw, db, scratch, st)
-                       : try_from_rgb_bwd<bf16_t>(B, R, C, img, down, w, c, gz_cs,
-                                                  (const bf16_t*)gz, gimg, ow, norms, dw, db, scratch,
-                                                  st)) == 0) {
-    PG_LAUNCH_CHECK();
-    return PG_OK;
-  }
-  if (gimg) {
-    const int Ri = down ? 2 * R : R;
-    const dim3 grid((Ri + 255) / 256, B * Ri);
-    PG_CHECK_ARG(!norms || pg_det_fits((size_t)grid.x * grid.y, 1), "from_rgb_bwd: too many rows");
-    if (dtype == PG_F32)
-      PG_KLAUNCH(from_rgb_dgrad_kernel<float>, grid, dim3(256), 0, st, R, C, down, w, c,
-                         gz_cs, (const float*)gz, gimg, ow, norms, B, scratch);
-    else
-      PG_KLAUNCH(from_rgb_dgrad_kernel<bf16_t>, grid, dim3(256), 0, st, R, C, down, w, c,
-                         gz_cs, (const bf16_t*)gz, gimg, ow, norms, B, scratch);
-  }
-  if (dw || db) {
-    const size_t npix = (size_t)B * R * R;
-    int ppb, blocks;
-    PG_CHECK_ARG(C <= 512, "from_rgb_bwd: C %d > 512", C);
-    rgb_wgrad_blocks(npix, 4 * C, &blocks, &ppb);
-    const int gb = (int)((npix + 255) / 256 < 1024 ? (npix + 255) / 256 : 1024);
-    if (dtype == PG_F32) {
-      if (C == 16)
-        PG_KLAUNCH((from_rgb_wgrad_small<float, 16>), dim3(gb), dim3(256), 0, st, B, R, img,
-                           down, c, gz_cs, (const float*)gz, dw, db, scratch);
-      else if (C == 32)
-        PG_KLAUNCH((from_rgb_wgrad_small<float, 32>), dim3(gb), dim3(256), 0, st, B, R, img,
-                           down, c, gz_cs, (const float*)gz, dw, db, scratch);
-      else
-        PG_KLAUNCH(from_rgb_wgrad_kernel<float>, dim3(blocks), dim3(256), 0, st, B, R, C,
-                           img, down, c, gz_cs, (const float*)gz, dw, db, ppb, scratch);
-    } else {
-      if (C == 16)
-        PG_KLAUNCH((from_rgb_wgrad_small<bf16_t, 16>), dim3(gb), dim3(256), 0, st, B, R,
-                           img, down, c, gz_cs, (const bf16_t*)gz, dw, db, scratch);
-      else if (C == 32)
-        PG_KLAUNCH((from_rgb_wgrad_small<bf16_t, 32>), dim3(gb), dim3(256), 0, st, B, R,
-                           img, down, c, gz_cs, (const bf16_t*)gz, dw, db, scratch);
-      else
-        PG_KLAUNCH(from_rgb_wgrad_kernel<bf16_t>, dim3(blocks), dim3(256), 0, st, B, R, C,
-                           img, down, c, gz_cs, (const bf16_t*)gz, dw, db, ppb, scratch);
+  const ImgSrc src = img ? ImgSrc(*img) : ImgSrc();
+  float* sc = (float*)scratch;
+  const int ow = gimg_overwrite;
+  hipStream_t st = (hipStream_t)stream;
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    if (try_from_rgb_bwd<T>(B, R, C, src, down, w, c, gz_cs, (const T*)gz, gimg, ow, norms, dw, db,
+                            sc, st) == 0)
+      return PG_OK;
+    if (gimg) {
+      const int Ri = down ? 2 * R : R;
+      const dim3 grid((Ri + 255) / 256, B * Ri);
+      PG_CHECK_ARG(!norms || pg_det_fits((size_t)grid.x * grid.y, 1), "from_rgb_bwd: too many rows");
+      PG_KLAUNCH(from_rgb_dgrad_kernel<T>, grid, dim3(256), 0, st, R, C, down, w, c, gz_cs,
+                 (const T*)gz, gimg, ow, norms, B, sc);
     }
-  }
+    if (dw || db) {
+      const size_t npix = (size_t)B * R * R;
+      int ppb, blocks;
+      PG_CHECK_ARG(C <= 512, "from_rgb_bwd: C %d > 512", C);
+      rgb_wgrad_blocks(npix, 4 * C, &blocks, &ppb);
+      const int gb = (int)((npix + 255) / 256 < 1024 ? (npix + 255) / 256 : 1024);
+      if (C == 16)
+        PG_KLAUNCH((from_rgb_wgrad_small<T, 16>), dim3(gb), dim3(256), 0, st, B, R, src, down, c,
+                   gz_cs, (const T*)gz, dw, db, sc);
+      else if (C == 32)
+        PG_KLAUNCH((from_rgb_wgrad_small<T, 32>), dim3(gb), dim3(256), 0, st, B, R, src, down, c,
+                   gz_cs, (const T*)gz, dw, db, sc);
+      else
+        PG_KLAUNCH(from_rgb_wgrad_kernel<T>, dim3(blocks), dim3(256), 0, st, B, R, C, src, down, c,
+                   gz_cs, (const T*)gz, dw, db, ppb, sc);
+    }
+    return PG_OK;
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
-}
-
-int pg_from_rgb_bwd(int dtype, int B, int R, int C, const float* img, int down, const float* w,
-                    float c, int gz_cs, const void* gz, float* gimg, float* dw, float* db,
-                    void* scratch, void* stream) {
-  return from_rgb_bwd_impl(dtype, B, R, C, ImgSrc(img), down, w, c, gz_cs, gz, gimg, 0, nullptr,
-                           dw, db, (float*)scratch, (hipStream_t)stream);
-}
-
-int pg_from_rgb_bwd_src(int dtype, int B, int R, int C, const pg_img_src* img, int down,
-                        const float* w, float c, int gz_cs, const void* gz, float* gimg,
-                        int gimg_overwrite, float* norms, float* dw, float* db, void* scratch,
-                        void* stream) {
-  PG_CHECK_ARG(!img || !img->x1 || (img->a && img->c), "from_rgb_bwd_src: bad image source");
-  return from_rgb_bwd_impl(dtype, B, R, C, img ? ImgSrc(*img) : ImgSrc(), down, w, c, gz_cs, gz,
-                           gimg, gimg_overwrite, norms, dw, db, (float*)scratch, (hipStream_t)stream);
 }
 
 int pg_penalty_scale(int mode, int B, float* norms, float w, float* loss_out, float* scale,
@@ -1717,69 +1594,62 @@ int pg_img_fade(int B, int C, int R, const float* x, float alpha, float* out, vo
   return PG_OK;
 }
 
-int pg_linear_fwd(int dtype, const pg_linear_desc* d, const void* x, const float* w,
-                  const float* b, const void* aux, void* y, void* stream) {
-  PG_CHECK_ARG(d && x && w && y && d->B > 0 && d->K > 0 && d->N > 0, "linear_fwd: bad args");
-  PG_CHECK_ARG(!(d->flags & PG_LIN_BIAS) || b, "linear_fwd: BIAS without bias");
-  PG_CHECK_ARG(!(d->flags & PG_LIN_MASK) || aux, "linear_fwd: MASK without aux");
-  hipStream_t st = (hipStream_t)stream;
-  // bf16: the coalesced kernels; f32 (the exact-parity mode) keeps the simple per-feature
-  // summation order, which the full-width parity tests pin (a different order moves
-  // near-zero leaky-relu inputs across the kink)
-  if (d->K % 16 == 0 && dtype == PG_BF16) {
-    DT_DISPATCH(dtype, linear_fwd_kernel2, dim3(d->N), dim3(256), 0, st, *d, x, w, b, aux, y);
-  } else {
-    const int wpb = 4;
-    DT_DISPATCH(dtype, linear_fwd_kernel, dim3(pg_cdiv(d->N, wpb)), dim3(64 * wpb), 0, st, *d, x,
-                w, b, aux, y);
-  }
-  PG_LAUNCH_CHECK();
-  return PG_OK;
-}
-
 size_t pg_linear_workspace_size(int dtype, const pg_linear_desc* d, int pass) {
   if (!d || !lin_fast_ok(dtype, d)) return 0;
   return pass == 0 ? lin_fwd_plan(d).ws_bytes : lin_dgrad_plan(d).ws_bytes;
 }
 
-int pg_linear_fwd_ws(int dtype, const pg_linear_desc* d, const void* x, const float* w,
-                     const float* b, const void* aux, void* y, void* ws, size_t ws_bytes,
-                     void* stream) {
+int pg_linear_fwd(int dtype, const pg_linear_desc* d, const void* x, const float* w,
+                  const float* b, const void* aux, void* y, void* ws, size_t ws_bytes,
+                  void* stream) {
   PG_CHECK_ARG(d && x && w && y && d->B > 0 && d->K > 0 && d->N > 0, "linear_fwd: bad args");
   PG_CHECK_ARG(!(d->flags & PG_LIN_BIAS) || b, "linear_fwd: BIAS without bias");
   PG_CHECK_ARG(!(d->flags & PG_LIN_MASK) || aux, "linear_fwd: MASK without aux");
-  if (!(ws && lin_fast_ok(dtype, d) && ws_bytes >= lin_fwd_plan(d).ws_bytes))
-    return pg_linear_fwd(dtype, d, x, w, b, aux, y, stream);
-  lin_fwd_fast<bf16_t>(d, x, w, b, aux, y, (float*)ws, (hipStream_t)stream);
-  PG_LAUNCH_CHECK();
-  return PG_OK;
-}
-
-int pg_linear_dgrad_ws(int dtype, const pg_linear_desc* d, const void* gy, const float* w,
-                       const void* aux, void* gx, void* ws, size_t ws_bytes, void* stream) {
-  PG_CHECK_ARG(d && gy && w && gx, "linear_dgrad: bad args");
-  PG_CHECK_ARG(!(d->flags & PG_LIN_MASK) || aux, "linear_dgrad: MASK without aux");
-  if (!(ws && lin_fast_ok(dtype, d) && ws_bytes >= lin_dgrad_plan(d).ws_bytes))
-    return pg_linear_dgrad(dtype, d, gy, w, aux, gx, stream);
-  lin_dgrad_fast<bf16_t>(d, gy, w, aux, gx, (float*)ws, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  if (ws && lin_fast_ok(dtype, d) && ws_bytes >= lin_fwd_plan(d).ws_bytes) {
+    lin_fwd_fast<bf16_t>(d, x, w, b, aux, y, (float*)ws, st);
+    PG_LAUNCH_CHECK();
+    return PG_OK;
+  }
+  // bf16: the coalesced kernels; f32 (the exact-parity mode) keeps the simple per-feature
+  // summation order, which the full-width parity tests pin (a different order moves
+  // near-zero leaky-relu inputs across the kink)
+  const bool coalesced = d->K % 16 == 0 && dtype == PG_BF16;
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    const int wpb = 4;
+    if (coalesced)
+      PG_KLAUNCH(linear_fwd_kernel2<T>, dim3(d->N), dim3(256), 0, st, *d, x, w, b, aux, y);
+    else
+      PG_KLAUNCH(linear_fwd_kernel<T>, dim3(pg_cdiv(d->N, wpb)), dim3(64 * wpb), 0, st, *d, x, w, b,
+                 aux, y);
+    return PG_OK;
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
 
 int pg_linear_dgrad(int dtype, const pg_linear_desc* d, const void* gy, const float* w,
-                    const void* aux, void* gx, void* stream) {
+                    const void* aux, void* gx, void* ws, size_t ws_bytes, void* stream) {
   PG_CHECK_ARG(d && gy && w && gx, "linear_dgrad: bad args");
   PG_CHECK_ARG(!(d->flags & PG_LIN_MASK) || aux, "linear_dgrad: MASK without aux");
-  const size_t n = (size_t)d->B * d->K;
   hipStream_t st = (hipStream_t)stream;
-  (void)n;
-  if (dtype != PG_BF16) {
-    DT_DISPATCH(dtype, linear_dgrad_kernel2, dim3(pg_cdiv(d->K, 64)), dim3(256), 0, st, *d, gy, w,
-                aux, gx);
-  } else {
-    DT_DISPATCH(dtype, linear_dgrad_kernel3, dim3(pg_cdiv(d->K, 64)), dim3(1024), 0, st, *d, gy, w,
-                aux, gx);
+  if (ws && lin_fast_ok(dtype, d) && ws_bytes >= lin_dgrad_plan(d).ws_bytes) {
+    lin_dgrad_fast<bf16_t>(d, gy, w, aux, gx, (float*)ws, st);
+    PG_LAUNCH_CHECK();
+    return PG_OK;
   }
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    if (dtype != PG_BF16)
+      PG_KLAUNCH(linear_dgrad_kernel2<T>, dim3(pg_cdiv(d->K, 64)), dim3(256), 0, st, *d, gy, w, aux, gx);
+    else
+      PG_KLAUNCH(linear_dgrad_kernel3<T>, dim3(pg_cdiv(d->K, 64)), dim3(1024), 0, st, *d, gy, w, aux,
+                 gx);
+    return PG_OK;
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
@@ -1803,7 +1673,12 @@ int pg_linear_wgrad(int dtype, const pg_linear_desc* d, const void* x, const voi
     PG_LAUNCH_CHECK();
     return PG_OK;
   }
-  DT_DISPATCH(dtype, linear_wgrad_kernel, dim3(grid_for(n)), dim3(256), 0, st, *d, x, gy, dw, db);
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    PG_KLAUNCH(linear_wgrad_kernel<decltype(t)>, dim3(grid_for(n)), dim3(256), 0, st, *d, x, gy, dw,
+               db);
+    return PG_OK;
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
@@ -1811,43 +1686,29 @@ int pg_linear_wgrad(int dtype, const pg_linear_desc* d, const void* x, const voi
 int pg_mbstd_fwd(int dtype, int B, int HW, int C, int x_cs, const void* x, int y_cs, void* y,
                  void* stream) {
   PG_CHECK_ARG(x && y && B > 0 && y_cs > C && x_cs >= C, "mbstd_fwd: bad args");
-  const int G = mbstd_group(B);
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == PG_F32)
-    PG_KLAUNCH(mbstd_fwd_kernel<float>, dim3(B / G, PG_MBSTD_SLICES), dim3(1024), 0, st, B, HW, C, x_cs,
-                       (const float*)x, y_cs, (float*)y);
-  else
-    PG_KLAUNCH(mbstd_fwd_kernel<bf16_t>, dim3(B / G, PG_MBSTD_SLICES), dim3(1024), 0, st, B, HW, C, x_cs,
-                       (const bf16_t*)x, y_cs, (bf16_t*)y);
+  const dim3 grid(B / mbstd_group(B), PG_MBSTD_SLICES);
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    PG_KLAUNCH(mbstd_fwd_kernel<T>, grid, dim3(1024), 0, (hipStream_t)stream, B, HW, C, x_cs,
+               (const T*)x, y_cs, (T*)y);
+    return PG_OK;
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
 
-}  // extern "C"
-
-// typed wrappers for the remaining mbstd entry points (DT_DISPATCH needs typed pointers)
-template <typename T>
-static void mbstd_bwd_launch(int B, int HW, int C, int x_cs, const void* x, int y_cs, const void* gy,
-                             void* gx, hipStream_t st) {
-  const int G = mbstd_group(B);
-  PG_KLAUNCH(mbstd_bwd_kernel<T>, dim3(B / G, PG_MBSTD_SLICES), dim3(1024), 0, st, B, HW, C, x_cs,
-                     (const T*)x, y_cs, (const T*)gy, (T*)gx);
-}
-template <typename T>
-static void mbstd_r1_launch(int B, int HW, int C, int x_cs, const void* x, const void* a, int y_cs,
-                            const void* gy, void* tout, void* inj, hipStream_t st) {
-  const int G = mbstd_group(B);
-  PG_KLAUNCH(mbstd_r1_kernel<T>, dim3(B / G, PG_MBSTD_SLICES), dim3(1024), 0, st, B, HW, C, x_cs, (const T*)x,
-                     (const T*)a, y_cs, (const T*)gy, (T*)tout, (T*)inj);
-}
-
-extern "C" {
-
 int pg_mbstd_bwd(int dtype, int B, int HW, int C, int x_cs, const void* x, int y_cs,
                  const void* gy, void* gx, void* stream) {
   PG_CHECK_ARG(x && gy && gx && B > 0 && y_cs > C, "mbstd_bwd: bad args");
-  if (dtype == PG_F32) mbstd_bwd_launch<float>(B, HW, C, x_cs, x, y_cs, gy, gx, (hipStream_t)stream);
-  else mbstd_bwd_launch<bf16_t>(B, HW, C, x_cs, x, y_cs, gy, gx, (hipStream_t)stream);
+  const dim3 grid(B / mbstd_group(B), PG_MBSTD_SLICES);
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    PG_KLAUNCH(mbstd_bwd_kernel<T>, grid, dim3(1024), 0, (hipStream_t)stream, B, HW, C, x_cs,
+               (const T*)x, y_cs, (const T*)gy, (T*)gx);
+    return PG_OK;
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
@@ -1855,10 +1716,14 @@ int pg_mbstd_bwd(int dtype, int B, int HW, int C, int x_cs, const void* x, int y
 int pg_mbstd_r1(int dtype, int B, int HW, int C, int x_cs, const void* x, const void* a, int y_cs,
                 const void* gy, void* tout, void* inj, void* stream) {
   PG_CHECK_ARG(x && a && gy && tout && inj && B > 0 && y_cs > C, "mbstd_r1: bad args");
-  if (dtype == PG_F32)
-    mbstd_r1_launch<float>(B, HW, C, x_cs, x, a, y_cs, gy, tout, inj, (hipStream_t)stream);
-  else
-    mbstd_r1_launch<bf16_t>(B, HW, C, x_cs, x, a, y_cs, gy, tout, inj, (hipStream_t)stream);
+  const dim3 grid(B / mbstd_group(B), PG_MBSTD_SLICES);
+  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
+    using T = decltype(t);
+    PG_KLAUNCH(mbstd_r1_kernel<T>, grid, dim3(1024), 0, (hipStream_t)stream, B, HW, C, x_cs,
+               (const T*)x, (const T*)a, y_cs, (const T*)gy, (T*)tout, (T*)inj);
+    return PG_OK;
+  });
+  if (rc != PG_OK) return rc;
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
@@ -1887,15 +1752,6 @@ int pg_r1_penalty(int B, size_t n, const float* g, float* r1_out, float* gbar, v
   PG_CHECK_ARG(g && r1_out && B > 0 && scratch, "r1_penalty: bad args (scratch required)");
   PG_KLAUNCH(r1_kernel, dim3(grid_for(n, 256, 1024)), dim3(256), 0, (hipStream_t)stream, B,
                      n, g, r1_out, gbar, (float*)scratch);
-  PG_LAUNCH_CHECK();
-  return PG_OK;
-}
-
-int pg_gp_interp(int B, size_t per, const float* xr, const float* xf, const float* eps,
-                 float* out, void* stream) {
-  PG_CHECK_ARG(xr && xf && eps && out, "gp_interp: bad args");
-  PG_KLAUNCH(gp_interp_kernel, dim3(grid_for((size_t)B * per)), dim3(256), 0,
-                     (hipStream_t)stream, B, per, xr, xf, eps, out);
   PG_LAUNCH_CHECK();
   return PG_OK;
 }

@@ -400,10 +400,6 @@ class CpuOps:
         r1 += 0.5 * (g * g).sum() / B
         gbar.copy_(g / B)
 
-    def gp_interp(self, xr, xf, eps, out):
-        e = eps.view(-1, 1, 1, 1)
-        out.copy_(e * xr + (1 - e) * xf)
-
     def gp_penalty(self, g, w, gp, norms, gbar):
         B = g.shape[0]
         n = g.reshape(B, -1).norm(dim=1)

@@ -51,3 +51,48 @@ def test_step_plan_on_the_host(lib):
     assert any(l.startswith("D b") and "1024x1024" in l and "conv_hr" in l for l in lines), text
     with pytest.raises(RuntimeError):
         ops.step_plan(depths, 9, 4)          # stage beyond the depth list
+
+
+def test_merged_entry_points_reject_bad_arguments(lib):
+    """The entry points that take their optional operand as a nullable argument refuse a flag
+    without its operand, the fused-RGB flags without their own entry point, and bad shapes,
+    on the host before any launch (the pointers here are never dereferenced), naming
+    themselves in the message.  Shapes: 16x16, B 1, 16 -> 16 channels."""
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    BF = _lib.PG_BF16
+
+    def desc(flags, H=16, aux_cs=0, xb_cs=0):
+        return ctypes.byref(_lib.ConvDesc(1, H, 16, 16, 16, 16, 16, aux_cs, 0, flags, 0.2, 1.0, xb_cs))
+
+    def fwd(d, xbits, aux=None, dtype=BF):
+        return lib.pg_conv3x3_fwd(dtype, d, p, xbits, p, None, aux, p, None, None, 0, None)
+
+    def from_rgb(src, mask_bits, ybits):
+        return lib.pg_from_rgb(BF, 1, 16, 16, ctypes.byref(src), 0, p, None, 1.0, 0.2, None,
+                               mask_bits, 16, p, ybits, None)
+
+    img = _lib.ImgSrcDesc(p.value, None, None, None)
+    mix = _lib.ImgSrcDesc(p.value, p.value, None, None)
+    lin = _lib.LinearDesc(1, 16, 16, 0, 0, _lib.LIN_BIAS, 1.0, 0.2)
+    rgbw = _lib.CONV_RGBW | _lib.CONV_MASK | _lib.CONV_AUX_BITS
+    calls = {
+        "conv3x3_fwd": [
+            lambda: fwd(desc(_lib.CONV_X_BITS, xb_cs=2), None),        # flag without xbits
+            lambda: fwd(desc(_lib.CONV_X_BITS, H=24, xb_cs=2), p),     # H not a power of two
+            lambda: fwd(desc(rgbw, aux_cs=2), None, aux=p),            # RGBW: own entry point
+            lambda: fwd(desc(0), None, dtype=7)],                      # no such dtype
+        "conv3x3_wgrad": [
+            lambda: lib.pg_conv3x3_wgrad(BF, desc(_lib.CONV_GZ_BITS, xb_cs=2), p, p, None, 1.0, p,
+                                         None, None, 0, None)],
+        "from_rgb": [lambda: from_rgb(img, p, p),                      # both bit operands
+                     lambda: from_rgb(mix, None, None)],               # x1 without a / c
+        "linear_fwd": [lambda: lib.pg_linear_fwd(BF, ctypes.byref(lin), p, p, None, None, p, None,
+                                                 0, None)],
+        "rgb_out_bwd_pn": [lambda: lib.pg_rgb_out_bwd_pn(BF, 1, 16, 16, 16, p, p, p, 1.0, p, 0.2, 16,
+                                                         p, p, None, None, None)],
+    }
+    for name, fns in calls.items():
+        for i, fn in enumerate(fns):
+            assert fn() == -1, (name, i)
+            assert name.encode() in lib.pg_last_error(), (name, i, lib.pg_last_error())

@@ -696,7 +696,7 @@ def test_sign_bit_conv_paths(B, H, c1, c2):
 def test_sign_bit_unpool_paths(B, H, c1, c2):
     """The conv-b sign bits below the full sign-bit resolution (engine._ubits, the wide LDS-DMA
     tile): forward with Y2_BITS|POOL, the R1 tangent with AUX_BITS|MASK|POOL against the CPU
-    double, and the unpool pass reading the bits (pg_unpool_mask_bits) bitwise equal to the
+    double, and the unpool pass reading the bits (pg_unpool_mask with bits) bitwise equal to the
     same pass reading the bf16 activation whose signs they are."""
     from cpu_ops import CONV_AUX_BITS, CONV_BIAS, CONV_LRELU, CONV_MASK, CONV_POOL, CONV_Y2_BITS
     hip, cpu = ops_pair(torch.bfloat16)
@@ -786,9 +786,9 @@ def test_rgb_out_bwd_pn(dtype, C, R):
 
 @pytest.mark.parametrize("C,R", [(16, 256), (32, 128), (16, 1024)])
 def test_from_rgb_sign_bits(C, R):
-    """pg_from_rgb_bits (bf16): the forward writes the lrelu sign bits of its output with the
-    same y as pg_from_rgb, and the tangent masked by those bits equals the tangent masked by
-    the bf16 activation (mask_y) bit for bit, and the CPU double."""
+    """pg_from_rgb with sign bits (bf16): the forward writes the lrelu sign bits of its output
+    with the same y as without them, and the tangent masked by those bits equals the tangent
+    masked by the bf16 activation (mask_y) bit for bit, and the CPU double."""
     hip, cpu = ops_pair(torch.bfloat16)
     B = 2
     img = rnd(B, 3, R, R, seed=71)
