@@ -429,6 +429,33 @@ int pg_swd_project(size_t n, const float* desc, const float* mean3, const float*
 int pg_swd_l1(int P, size_t n, const float* a, const float* b, size_t stride, float* out,
               void* scratch, void* stream);
 
+/* ---- multi-scale structural similarity between image pairs (the PGGAN paper's diversity
+ * metric; DESIGN.md "Validation: MS-SSIM").  All fp32; images NCHW [3][S][S].
+ * One scale of P pairs.  a / b: the two sides of the first pair, the two sides of pair p at
+ * a + p * img_stride and b + p * img_stride (floats; pairs interleaved in one [2P][3][S][S]
+ * batch: b = a + 3 S^2, img_stride = 6 S^2).  `quantize` != 0 reads the images as 8-bit like
+ * pg_swd_pyr_down (scale 0), otherwise they are taken as they are, on the 0..255 scale.
+ * taps: T window weights (HOST memory, read during the call), 1 <= T <= min(11, S); the 2-D
+ * window is taps (x) taps, filtering is "valid": n = S - T + 1 positions per axis.  With F the
+ * filter, mu1 = F(a), mu2 = F(b), s11 = F(a a) - mu1^2, s22 = F(b b) - mu2^2, s12 = F(a b) -
+ * mu1 mu2, c1 = 2.55^2, c2 = 7.65^2, v1 = 2 s12 + c2, v2 = s11 + s22 + c2:
+ *   sums[p][0] = sum over the 3 n^2 positions of (2 mu1 mu2 + c1) v1 / ((mu1^2 + mu2^2 + c1) v2)
+ *   sums[p][1] = sum over the 3 n^2 positions of v1 / v2
+ * (fp32 partials per workgroup in `ws`, combined in double in a fixed order).  pool_a / pool_b
+ * [P][3][S/2][S/2], both or neither: the aligned 2x2 means of the two sides as read (after
+ * `quantize`), the next scale's input; S must be even.  ws: pg_msssim_workspace_bytes(P, S, T)
+ * of device memory.  P <= 65535.  16-byte loads when S % 4 == 0 and a, b, img_stride and the
+ * pooled outputs are 16-byte aligned, scalar loads otherwise. */
+size_t pg_msssim_workspace_bytes(int P, int S, int T);
+int pg_msssim_scale(int P, int S, int T, const float* taps, const float* a, const float* b,
+                    size_t img_stride, int quantize, float* sums, float* pool_a, float* pool_b,
+                    void* ws, size_t ws_bytes, void* stream);
+/* out[p] = prod_{s < 4} max(cs_s, 0)^w_s * max(ssim_4, 0)^w_4 with ssim_s = sums[s][p][0] /
+ * counts[s], cs_s = sums[s][p][1] / counts[s], w = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333);
+ * sums [5][P][2] from five pg_msssim_scale calls, counts: the five 3 n_s^2 (HOST memory),
+ * evaluated in double. */
+int pg_msssim_combine(int P, const float* sums, const long long* counts, float* out, void* stream);
+
 /* ---- stream ordering between the engine's streams (weight gradients on a side stream).
  * torch's cross-stream events record with a system-scope release: every record writes back and
  * invalidates the L2 of all XCDs and the next kernel on that stream starts ~6.5 us late.  The

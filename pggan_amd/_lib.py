@@ -155,6 +155,9 @@ _SIGS = {
     "pg_swd_stats": ([_SZ, _VP, _VP, _VP, _VP, _VP], _I),
     "pg_swd_project": ([_SZ, _VP, _VP, _VP, _I, _VP, _VP, _SZ, _VP], _I),
     "pg_swd_l1": ([_I, _SZ, _VP, _VP, _SZ, _VP, _VP, _VP], _I),
+    "pg_msssim_workspace_bytes": ([_I, _I, _I], _SZ),
+    "pg_msssim_scale": ([_I, _I, _I, _VP, _VP, _VP, _SZ, _I, _VP, _VP, _VP, _VP, _SZ, _VP], _I),
+    "pg_msssim_combine": ([_I, _VP, _VP, _VP, _VP], _I),
     "pg_step_plan_create": ([_I, _I, ctypes.POINTER(ctypes.c_int), _I, _I,
                              ctypes.POINTER(ctypes.c_void_p)], _I),
     "pg_step_plan_workspace_size": ([_VP], _SZ),
@@ -755,7 +758,7 @@ class HipOps:
         self._cuda(*ts)
         for t in ts:
             if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-                raise RuntimeError("pggan_amd: the swd ops take contiguous fp32 tensors")
+                raise RuntimeError("pggan_amd: the swd and msssim ops take contiguous fp32 tensors")
 
     def swd_pyr_down(self, x, y, quantize):
         """x [B,3,S,S] -> y [B,3,S/2,S/2]: one Gaussian pyramid step (pg_swd_pyr_down)."""
@@ -796,6 +799,43 @@ class HipOps:
         assert a.shape == b.shape
         self._chk(self.lib.pg_swd_l1(a.shape[0], n, _p(a), _p(b), a.shape[1], _p(out), self._scr(),
                                      self._s()), "swd_l1")
+
+    # -- multi-scale structural similarity (pggan_amd/metrics.py, csrc/msssim.hip) ----
+    def msssim_scale(self, a, b, taps, quantize, sums, pool_a=None, pool_b=None):
+        """One scale of P pairs (pg_msssim_scale).  a, b [P,3,S,S]: the two sides, each image
+        contiguous, the same batch stride on both (two interleaved views x[0::2], x[1::2] of
+        one batch need no copy); taps: the T window weights (a sequence of floats); sums
+        [P,2] = (sum ssim, sum cs) per pair; pool_a / pool_b [P,3,S/2,S/2]: the next scale."""
+        self._f32c(sums, pool_a, pool_b)
+        self._cuda(a, b)
+        P, _, S, _ = a.shape
+        for t in (a, b):
+            if t.dtype != torch.float32 or tuple(t.shape) != (P, 3, S, S) or \
+                    tuple(t.stride()[1:]) != (S * S, S, 1) or (P > 1 and t.stride(0) != a.stride(0)):
+                raise RuntimeError("pggan_amd: msssim_scale takes fp32 [P,3,S,S] sides with "
+                                   "contiguous images and one batch stride")
+        assert sums.numel() == 2 * P
+        assert pool_a is None or pool_a.numel() == pool_b.numel() == P * 3 * (S // 2) ** 2
+        T = len(taps)
+        tp = (ctypes.c_float * max(T, 1))(*[float(v) for v in taps])
+        need = int(self.lib.pg_msssim_workspace_bytes(P, S, T))
+        ws = getattr(self, "_msws", None)
+        if ws is None or ws.numel() * 4 < need or ws.device != a.device:
+            ws = self._msws = torch.empty(max(need // 4, 1), dtype=torch.float32, device=a.device)
+        stride = a.stride(0) if P > 1 else 3 * S * S
+        self._chk(self.lib.pg_msssim_scale(P, S, T, tp, _p(a), _p(b), stride, 1 if quantize else 0,
+                                           _p(sums), _p(pool_a), _p(pool_b), _p(ws),
+                                           ws.numel() * 4, self._s()), "msssim_scale")
+
+    def msssim_combine(self, sums, counts, out):
+        """out [P] = the pair values from sums [5,P,2] and the five counts 3 n_s^2
+        (pg_msssim_combine)."""
+        self._f32c(sums, out)
+        P = out.numel()
+        assert sums.numel() == 10 * P and len(counts) == 5
+        cn = (ctypes.c_longlong * 5)(*[int(v) for v in counts])
+        self._chk(self.lib.pg_msssim_combine(P, _p(sums), cn, _p(out), self._s()),
+                  "msssim_combine")
 
     def cast(self, x, y):
         self._cuda(x, y)

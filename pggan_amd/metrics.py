@@ -12,9 +12,13 @@ calls torch.sort for the sort.
     for batch in reals: m.feed("real", batch)      # fp32 [B, 3, 256, 256] in [-1, 1]
     for batch in fakes: m.feed("fake", batch)
     m.result()   # {256: v, 128: v, 64: v, 32: v, 16: v, "avg": v}, x 1e3 as the paper prints
+
+And the paper's second figure, the multi-scale structural similarity between pairs of images of
+one set (MultiScaleSSIM below; csrc/msssim.hip through the op set's msssim_* methods).
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 DESC = 147                   # 7 x 7 x 3 values per descriptor
@@ -138,3 +142,102 @@ class SlicedWasserstein:
         out = dict(zip(self.sizes, vals))
         out["avg"] = sum(vals) / len(vals)
         return out
+
+
+# ---------------------------------------------------------------------------------- MS-SSIM
+MSSSIM_SCALES = 5
+MSSSIM_WINDOW = 11           # taps per axis at scales of at least that side
+MSSSIM_SIGMA = 1.5           # of the 11-tap window; shorter windows scale it with their length
+
+
+def msssim_taps(size):
+    """The 1-D Gaussian window of a scale of side `size`: T = min(11, size) taps centred on
+    (T - 1) / 2 (half-integer positions for an even T), sigma = 1.5 T / 11, normalised to sum 1
+    in float64; returned as fp32 (what the kernel takes)."""
+    T = min(MSSSIM_WINDOW, int(size))
+    sigma = MSSSIM_SIGMA * T / MSSSIM_WINDOW
+    d = np.arange(T, dtype=np.float64) - (T - 1) / 2.0
+    g = np.exp(-d * d / (2.0 * sigma * sigma))
+    return (g / g.sum()).astype(np.float32)
+
+
+class MultiScaleSSIM:
+    """The PGGAN paper's diversity figure: multi-scale structural similarity (Wang et al. 2003;
+    five scales, 11x11 Gaussian windows, 8-bit images) between `n_pairs` pairs of images of one
+    stream, consecutive images paired (0,1), (2,3), ..  (DESIGN.md "Validation: MS-SSIM").
+    Every scale is one launch of the library (csrc/msssim.hip through the op set's msssim_*
+    methods) that also writes the next scale's 2x2-pooled pair; the host side pairs the images up.
+
+        m = MultiScaleSSIM(ops, 256, 10000)
+        for batch in fakes: m.feed(batch)       # fp32 [B, 3, 256, 256] in [-1, 1]
+        m.result()                              # mean over the pairs, in [0, 1]
+
+    quantize=False takes the images as they are, on the 0..255 scale.  Work buffers: the four
+    pooled scales of a batch's pairs, allocated once for the largest batch seen."""
+
+    def __init__(self, ops, resolution, n_pairs, quantize=True):
+        R = int(resolution)
+        if R < 16 or R & (R - 1):
+            raise ValueError(f"MultiScaleSSIM: resolution must be a power of two >= 16, got {R}")
+        if int(n_pairs) < 1:
+            raise ValueError("MultiScaleSSIM: n_pairs must be >= 1")
+        self.ops, self.R, self.n_pairs, self.quantize = ops, R, int(n_pairs), bool(quantize)
+        self.sizes = [R >> s for s in range(MSSSIM_SCALES)]
+        self.taps = [msssim_taps(s) for s in self.sizes]
+        self.counts = [3 * (s - len(t) + 1) ** 2 for s, t in zip(self.sizes, self.taps)]
+        self.fed = 0                 # images taken so far, the held one included
+        self.sums = None             # [5, n_pairs, 2] on the device of the first images fed
+        self._held = None            # a trailing odd image waiting for its partner
+        self._pool = []              # per later scale [2, P, 3, S, S] for the largest P seen
+
+    def feed(self, images):
+        if images.dim() != 4 or tuple(images.shape[1:]) != (3, self.R, self.R):
+            raise ValueError(f"MultiScaleSSIM.feed: expected [B, 3, {self.R}, {self.R}], got "
+                             f"{tuple(images.shape)}")
+        B = images.shape[0]
+        if self.fed + B > 2 * self.n_pairs:
+            raise ValueError(f"MultiScaleSSIM.feed: {self.fed} + {B} images exceed 2 * n_pairs = "
+                             f"{2 * self.n_pairs}")
+        if B == 0:
+            return
+        x = images.detach().to(torch.float32)
+        if self.sums is None:
+            self.sums = torch.zeros(MSSSIM_SCALES, self.n_pairs, 2, dtype=torch.float32,
+                                    device=x.device)
+        first = (self.fed - (self._held is not None)) // 2      # pairs done so far
+        if self._held is not None:
+            x = torch.cat([self._held, x])
+            self._held = None
+        self.fed += B
+        P = x.shape[0] // 2
+        if x.shape[0] % 2:
+            self._held = x[-1:].clone()
+        if P == 0:
+            return
+        x = x[:2 * P].contiguous()
+        if not self._pool or self._pool[0].shape[1] < P:
+            self._pool = [torch.empty(2, P, 3, s, s, dtype=torch.float32, device=x.device)
+                          for s in self.sizes[1:]]
+        a, b = x[0::2], x[1::2]
+        for s in range(MSSSIM_SCALES):
+            last = s == MSSSIM_SCALES - 1
+            pa, pb = (None, None) if last else (self._pool[s][0, :P], self._pool[s][1, :P])
+            self.ops.msssim_scale(a, b, self.taps[s], self.quantize and s == 0,
+                                  self.sums[s, first:first + P], pa, pb)
+            a, b = pa, pb
+
+    def _check_full(self, what):
+        if self.fed != 2 * self.n_pairs:
+            raise RuntimeError(f"MultiScaleSSIM.{what}: {self.fed} of {2 * self.n_pairs} images fed")
+
+    def values(self):
+        """The per-pair values, fp32 [n_pairs]."""
+        self._check_full("values")
+        out = torch.empty(self.n_pairs, dtype=torch.float32, device=self.sums.device)
+        self.ops.msssim_combine(self.sums, self.counts, out)
+        return out
+
+    def result(self):
+        """The mean over the pairs, taken in float64."""
+        self._check_full("result")
+        return float(self.values().double().mean().item())

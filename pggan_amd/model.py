@@ -18,7 +18,8 @@ Differences (deliberate):
     weights the paper samples from (the reference dropped it): updated inside the Adam_G
     launch, sampled by `sample(z)`, saved beside the reference's files as `G_ema_*.pt`.
   * config `use_validation` fills in the reference's empty validation(): the paper's sliced
-    Wasserstein distance on the held-out 30 % of the images (pggan_amd.metrics).
+    Wasserstein distance on the held-out 30 % of the images (pggan_amd.metrics); config
+    `msssim_pairs` (blank: off) adds the paper's MS-SSIM between pairs of generated images.
 """
 from __future__ import annotations
 
@@ -321,13 +322,21 @@ class ProgressiveGAN:
     # ------------------------------------------------------------------ validation
     def set_validation(self):
         """Config `use_validation`: the paper's sliced Wasserstein distance between `swd_images`
-        reals and as many generated images (pggan_amd.metrics), every `valid_cycle` steps."""
+        reals and as many generated images (pggan_amd.metrics), every `valid_cycle` steps; with
+        `msssim_pairs` also the paper's MS-SSIM over that many pairs of the same images."""
         self._val = None
         if not cfg_get(self.args, "use_validation", False):
             return
         self._val = dict(images=int(cfg_get(self.args, "swd_images", None) or 4096),
                          seed=int(cfg_get(self.args, "swd_seed", None) or 0))
         self.valid_cycle = int(cfg_get(self.args, "valid_cycle", None) or self.args.ckpt_cycle)
+        pairs = cfg_get(self.args, "msssim_pairs", None)
+        if pairs:       # blank: no MS-SSIM
+            pairs = int(pairs)
+            if pairs < 1 or 2 * pairs > self._val["images"]:
+                raise ValueError(f"msssim_pairs: {pairs} pairs need 2 * {pairs} of the swd_images = "
+                                 f"{self._val['images']} images of a set")
+            self._val["msssim_pairs"] = pairs
 
     def _valid_reals(self, R, n, B):
         """n validation reals at R x R as fp32 [-1, 1] batches of at most B: the images under
@@ -361,7 +370,11 @@ class ProgressiveGAN:
         the averaged generator (G itself without `ema_decay`): {R: v, .., 16: v, "avg": v},
         printed on the master and appended to {save_root}/{run_id}/swd.csv as
         step,scale,levels..,avg.  None with `use_validation` off and below 16 x 16.  Reads the
-        generator through sample() only; draws from private generators."""
+        generator through sample() only; draws from private generators.
+        With `msssim_pairs` the first 2 * msssim_pairs images of each set also go through
+        MultiScaleSSIM: "msssim" (the generated images' mean pair similarity: lower is more
+        diverse) and "msssim_real" (the data's own, what the former is read against) join the
+        dict, are printed, and appended to msssim.csv as step,scale,msssim,msssim_real."""
         val = getattr(self, "_val", None)
         if val is None:
             return None
@@ -378,12 +391,23 @@ class ProgressiveGAN:
             ops = val["ops"] = (type(self).ops_factory or _lib.HipOps)(torch.float32)
         n, B = val["images"], int(self.args.batch_per_gpu)
         swd = SlicedWasserstein(ops, R, n, seed=val["seed"])
+        pairs = val.get("msssim_pairs")
+        ms = None
+        if pairs:       # the first 2 * pairs images of each set, as they pass by
+            from .metrics import MultiScaleSSIM
+            ms = {w: MultiScaleSSIM(ops, R, pairs) for w in ("real", "fake")}
+
+        def feed(which, x):
+            swd.feed(which, x)
+            if ms is not None and ms[which].fed < 2 * pairs:
+                ms[which].feed(x[:2 * pairs - ms[which].fed])
+
         for x in self._valid_reals(R, n, B):
-            swd.feed("real", x)
+            feed("real", x)
         g = torch.Generator().manual_seed(val["seed"])
         for i in range(0, n, B):     # always whole batches: one sampling engine shape
             z = torch.randn(B, self.args.latent_dim, generator=g).to(self.device)
-            swd.feed("fake", self.sample(z, ema=self.G_ema is not None)[:n - i])
+            feed("fake", self.sample(z, ema=self.G_ema is not None)[:n - i])
         out = swd.result()
         levels = [out[k] for k in swd.sizes]
         if master:
@@ -394,6 +418,13 @@ class ProgressiveGAN:
         with open(f"{d}/swd.csv", "a") as f:
             f.write(",".join([str(step), str(self.scale_index)] +
                              [repr(v) for v in levels + [out["avg"]]]) + "\n")
+        if ms is not None:
+            out["msssim"], out["msssim_real"] = ms["fake"].result(), ms["real"].result()
+            if master:
+                print(f"step {step}: MS-SSIM {out['msssim']:.4f} (reals {out['msssim_real']:.4f})")
+            with open(f"{d}/msssim.csv", "a") as f:
+                f.write(",".join([str(step), str(self.scale_index), repr(out["msssim"]),
+                                  repr(out["msssim_real"])]) + "\n")
         return out
 
     # ------------------------------------------------------------------ step

@@ -93,7 +93,55 @@ def wgrad_halo(HS, PADE, TW, TH, BP=128):
     return tot / n
 
 
+W128_GROUPS = [list(range(g, g + 8)) for g in range(0, 64, 8)]      # ds_write_b128
+
+
+def masked_cycles(addrs, groups, nbanks, dwords):
+    """As cycles() for an access of `dwords` dwords per lane with `nbanks` banks; a lane whose
+    address is None is inactive.  Returns (LDS cycles, lane groups with an active lane)."""
+    total = n = 0
+    for grp in groups:
+        banks = {}
+        for ln in grp:
+            if addrs[ln] is None:
+                continue
+            for k in range(dwords):
+                dw = addrs[ln] // 4 + k
+                banks.setdefault(dw % nbanks, set()).add(dw)
+        if banks:
+            total += max(len(v) for v in banks.values())
+            n += 1
+    return total, n
+
+
+def msssim(IW, HP, RP, IH=42, NJ=8):
+    """csrc/msssim.hip: the horizontal pass' item i = (row i % RP, column group i // RP), rows
+    >= IH idle, reads 16-B vectors of s_in (row pitch IW dwords, 64 banks) and writes 16-B
+    vectors of s_h (row pitch HP, 32 banks); the vertical pass reads one s_h row per 32 lanes
+    (consecutive dwords: conflict free at any pitch).  Returns wave passes over the items and
+    the mean LDS cycles per lane group of a read and of a write (1.0 = conflict free)."""
+    rd = wr = nr = nw = passes = 0
+    for w0 in range(0, RP * NJ, 64):
+        ra, wa = [], []
+        for i in range(w0, w0 + 64):
+            r, j = i % RP, i // RP
+            live = i < RP * NJ and r < IH
+            ra.append((r * IW + 4 * j) * 4 if live else None)
+            wa.append((r * HP + 4 * j) * 4 if live else None)
+        c, n = masked_cycles(ra, B128_GROUPS, 64, 4)
+        rd, nr = rd + c, nr + n
+        c, n = masked_cycles(wa, W128_GROUPS, 32, 4)
+        wr, nw = wr + c, nw + n
+        passes += 1
+    return {"passes": passes, "h_read": round(rd / nr, 3), "h_write": round(wr / nw, 3)}
+
+
 if __name__ == "__main__":
+    print("msssim (s_in pitch IW, s_h pitch HP, item rows per column group RP):")
+    for RP in (42, 48, 64):
+        for IW in (44, 48):
+            for HP in (32, 36):
+                print(f"  RP {RP} IW {IW} HP {HP}:", msssim(IW, HP, RP))
     print("wgrad halo (rows of BC=16 / 32 channels):")
     for TW, TH in ((16, 8), (8, 8), (4, 4)):
         for HS in (16, 32, 48):
