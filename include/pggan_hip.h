@@ -399,6 +399,30 @@ size_t pg_augment_workspace_bytes(int B, int H, int W);
 int pg_augment_u8(int B, int H, int W, const void* src, const float* params, float* ws,
                   size_t ws_bytes, float* dst, void* stream);
 
+/* ---- training-image resize (lib/dataset.py:103, Resize((S, S)) on the PIL image = Pillow's
+ * Image.resize(.., BILINEAR)): n uint8 RGB images of one source shape [Hin][Win][3] ->
+ * [S][S][3] in Pillow's 8-bit arithmetic (libImaging/Resample.c), byte-identical to PIL: a
+ * horizontal pass into a uint8 image [Hin][S][3], then a vertical pass, each
+ *   out = clip8((2^21 + sum_{x < count} pixel[xmin + x] * k[x]) >> 22)   (int32 sums)
+ * with per output position the window (xmin, count) and the 22-bit fixed-point weights k from
+ * the caller's tables: kx int32 [S][ksx], bx int32 [S][2] = (xmin, count) for Win -> S, ky / by
+ * / ksy for Hin -> S (DEVICE; built on the host in float64 as Pillow builds them, see
+ * pggan_amd.data.resize_coeffs; xmin + count <= the input size and count <= ks, the caller's
+ * duty).  As in Pillow a pass whose input size equals S is skipped (its tables are not read and
+ * may be NULL); with both skipped the call is a copy.
+ * Image i is read at src_base + src_off[i] and written at dst_base + dst_off[i] (src_off /
+ * dst_off: DEVICE int64 [n], byte offsets: rows of a ragged source cache, scattered rows of a
+ * batch).  Source rows are 3 Win bytes, unpadded; every source image starts 16-byte aligned;
+ * destinations need no alignment and must not overlap.  Every source byte is read from memory
+ * once.  ws: pg_resize_workspace_bytes(n, Hin, Win, S) of device workspace, 16-byte aligned (0
+ * bytes when a pass is skipped; ws may then be NULL).  n <= 65535; PG_ERR_UNSUPPORTED when 8
+ * source rows (24 Win bytes) do not fit the 64 KiB staging of the horizontal pass. */
+size_t pg_resize_workspace_bytes(int n, int Hin, int Win, int S);
+int pg_resize_bilinear_u8(int n, int Hin, int Win, int S, const void* src_base,
+                          const int64_t* src_off, const int* kx, const int* bx, int ksx,
+                          const int* ky, const int* by, int ksy, void* dst_base,
+                          const int64_t* dst_off, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- sliced Wasserstein distance on Laplacian-pyramid patches (the PGGAN paper's validation
  * metric; DESIGN.md "Validation: sliced Wasserstein distance").  All fp32; images NCHW
  * [B][3][S][S], S a power of two.  `quantize` != 0 reads the image as 8-bit:

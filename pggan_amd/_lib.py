@@ -150,6 +150,9 @@ _SIGS = {
     "pg_cast": ([_I, _I, _SZ, _VP, _VP, _VP], _I),
     "pg_augment_workspace_bytes": ([_I, _I, _I], _SZ),
     "pg_augment_u8": ([_I, _I, _I, _VP, _VP, _VP, _SZ, _VP, _VP], _I),
+    "pg_resize_workspace_bytes": ([_I, _I, _I, _I], _SZ),
+    "pg_resize_bilinear_u8": ([_I, _I, _I, _I, _VP, _VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _VP,
+                               _SZ, _VP], _I),
     "pg_swd_pyr_down": ([_I, _I, _I, _VP, _I, _VP, _VP], _I),
     "pg_swd_descriptors": ([_I, _I, _VP, _VP, _I, _VP, _I, _VP, _VP], _I),
     "pg_swd_stats": ([_SZ, _VP, _VP, _VP, _VP, _VP], _I),
@@ -751,6 +754,41 @@ class HipOps:
             ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=src.device)
         self._chk(self.lib.pg_augment_u8(B, H, W, _p(src), _p(params), _p(ws), ws.numel() * 4,
                                          _p(dst), self._s()), "augment_u8")
+        return ws
+
+    def resize_u8(self, src, src_off, Hin, Win, S, tab_x, tab_y, dst, dst_off, ws=None):
+        """Pillow's BILINEAR Resize((S, S)) of n uint8 RGB images [Hin,Win,3] (pg_resize_bilinear_u8,
+        lib/dataset.py:103).  src / dst: uint8 buffers; image i is read at byte src_off[i] of src
+        (16-byte aligned) and written at byte dst_off[i] of dst (int64 [n] device tensors).
+        tab_x / tab_y: the (weights int32 [S,ks], bounds int32 [S,2]) device tables of
+        pggan_amd.data.resize_coeffs for Win -> S / Hin -> S, None for an axis already at S.
+        Returns the workspace (pass it back in to reuse it)."""
+        self._cuda(src, src_off, dst, dst_off)
+        n = src_off.numel()
+        for t, dt in ((src, torch.uint8), (dst, torch.uint8), (src_off, torch.int64),
+                      (dst_off, torch.int64)):
+            if t.dtype != dt or not t.is_contiguous():
+                raise RuntimeError("pggan_amd: resize_u8 takes contiguous uint8 buffers and int64 offsets")
+        if dst_off.numel() != n or (tab_x is None) != (Win == S) or (tab_y is None) != (Hin == S):
+            raise RuntimeError("pggan_amd: resize_u8: one offset pair per image, tables for exactly "
+                               "the axes that change size")
+        tabs = []
+        for tab, n_in in ((tab_x, Win), (tab_y, Hin)):
+            if tab is None:
+                tabs += [None, None, 0]
+                continue
+            k, b = tab
+            self._cuda(k, b)
+            if k.dtype != torch.int32 or b.dtype != torch.int32 or not k.is_contiguous() or \
+                    not b.is_contiguous() or k.shape[0] != S or tuple(b.shape) != (S, 2):
+                raise RuntimeError(f"pggan_amd: resize_u8: bad coefficient table for {n_in} -> {S}")
+            tabs += [_p(k), _p(b), k.shape[1]]
+        need = int(self.lib.pg_resize_workspace_bytes(n, Hin, Win, S))
+        if need and (ws is None or ws.numel() < need or ws.device != src.device):
+            ws = torch.empty(need, dtype=torch.uint8, device=src.device)
+        self._chk(self.lib.pg_resize_bilinear_u8(n, Hin, Win, S, _p(src), _p(src_off), *tabs, _p(dst),
+                                                 _p(dst_off), _p(ws) if need else None,
+                                                 ws.numel() if need else 0, self._s()), "resize_u8")
         return ws
 
     # -- sliced Wasserstein distance (pggan_amd/metrics.py, csrc/swd.hip) ----

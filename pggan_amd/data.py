@@ -24,10 +24,20 @@ host decode -- 344 img/s from 1024^2 PNG on the box's 16 threads, below the step
 every stage (profiles/r4_loader.json) -- no longer bounds training.  The bytes the augmentation
 reads are the ones it would have decoded, so the output stays byte-exact.  Sizes: 3 S^2 bytes
 per image (3 MiB at 1024^2, 192 KiB at 256^2); a DP rank caches only its own shard.
+
+Source cache (`HbmSourceCache`, config hbm_source_cache_gb, opt-in): the cache above starts
+empty at every stage, so the first epoch of each of the 9 stages decodes every file again, and
+only the Resize differs.  With the source cache the decoded image is kept at source size in HBM
+too, and a stage's image comes from `pg_resize_bilinear_u8` (pggan_amd/csrc/resize.hip): Pillow's
+8-bit BILINEAR resize is integer arithmetic on fixed-point coefficient tables (`resize_coeffs`
+builds them in float64 as libImaging/Resample.c does), so the kernel's bytes are PIL's
+(tests/test_gpu_resize.py) and no stage after the first touches the disk or the host threads.
 """
 from __future__ import annotations
 
+import functools
 import glob
+import math
 import os
 from concurrent.futures import ThreadPoolExecutor
 
@@ -56,6 +66,71 @@ def load_u8(path, size):
     from PIL import Image
     im = Image.open(path).convert("RGB").resize((size, size), Image.BILINEAR)
     return np.asarray(im, dtype=np.uint8)
+
+
+def load_src_u8(path):
+    """Decode only -> uint8 [H, W, 3] at the file's own size (what load_u8 resizes)."""
+    from PIL import Image
+    return np.array(Image.open(path).convert("RGB"), dtype=np.uint8)   # a writable copy: pinned next
+
+
+def image_size(path):
+    """(H, W) from the file's header; nothing is decoded."""
+    from PIL import Image
+    with Image.open(path) as im:
+        w, h = im.size
+    return h, w
+
+
+RESIZE_BITS = 32 - 8 - 2   # Pillow's PRECISION_BITS: 8-bit pixels, 2 bits of headroom
+
+
+@functools.lru_cache(maxsize=None)
+def resize_coeffs(in_size, out_size):
+    """The coefficient tables of Pillow's 8-bit BILINEAR resize of one axis, in_size ->
+    out_size (libImaging/Resample.c precompute_coeffs + normalize_coeffs_8bpc, operation for
+    operation in float64: Python floats are C doubles) -> (k int32 [out, ksize], bounds int32
+    [out, 2] = (first tap, tap count)); taps past the count are 0.  Output pixel xx is
+    clip8((2^21 + sum_x pixel[xmin + x] * k[xx, x]) >> 22)."""
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = fs                       # bilinear: support 1.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    k = np.zeros((out_size, ksize), np.int32)
+    bounds = np.zeros((out_size, 2), np.int32)
+    for xx in range(out_size):
+        c = (xx + 0.5) * scale
+        xmin = max(int(c - support + 0.5), 0)
+        xmax = min(int(c + support + 0.5), in_size) - xmin
+        w = [max(0.0, 1.0 - abs((x + xmin - c + 0.5) / fs)) for x in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        for x, v in enumerate(w):
+            if ww != 0.0:
+                v /= ww
+            k[xx, x] = int(0.5 + v * (1 << RESIZE_BITS))
+        bounds[xx] = (xmin, xmax)
+    k.setflags(write=False)
+    bounds.setflags(write=False)
+    return k, bounds
+
+
+_DEV_COEFFS = {}   # (in, out, device) -> the tables on the device, uploaded once
+
+
+def device_resize_coeffs(in_size, out_size, device):
+    """resize_coeffs(in_size, out_size) as device tensors; None when the axis keeps its size
+    (Pillow skips that pass)."""
+    if in_size == out_size:
+        return None
+    key = (in_size, out_size, str(device))
+    t = _DEV_COEFFS.get(key)
+    if t is None:
+        k, b = resize_coeffs(in_size, out_size)
+        t = _DEV_COEFFS[key] = (torch.from_numpy(k.copy()).to(device),
+                                torch.from_numpy(b.copy()).to(device))
+    return t
 
 
 def draw_params(B, gen):
@@ -89,6 +164,9 @@ class ImageFolderDataset:
     def load(self, i):
         return load_u8(self.paths[i], self.size)
 
+    def load_src(self, i):
+        return load_src_u8(self.paths[i])
+
 
 class HbmImageCache:
     """The decoded + resized uint8 images of one dataset at one size, in HBM: slot table
@@ -121,6 +199,49 @@ class HbmImageCache:
         return k
 
 
+class HbmSourceCache:
+    """The decoded RGB images of a dataset at their source size, in HBM: one flat uint8 buffer
+    of `budget_bytes`, images keyed by path at 16-byte aligned offsets in first-decode order
+    until the budget is used.  Room is reserved from the header's size when a decode is
+    submitted (`reserve`), the pixels arrive later (`fill`); an image that no longer fits is
+    not cached and keeps the host path.  The cache belongs to the model, not to a stage: every
+    stage's BatchLoader resizes from it on the GPU (pg_resize_bilinear_u8)."""
+
+    ALIGN = 16
+
+    def __init__(self, device, budget_bytes):
+        self.dev = torch.device(device)
+        self.budget = int(max(0, budget_bytes))
+        self.buf = torch.empty(self.budget, dtype=torch.uint8, device=self.dev)
+        self.entries = {}    # path -> [offset, H, W, filled]
+        self.used = 0        # bytes reserved so far (the next offset)
+
+    def reserve(self, path, size_fn=image_size):
+        """The entry of `path`, reserving room for it on first sight; None if it does not fit."""
+        e = self.entries.get(path)
+        if e is None:
+            h, w = size_fn(path)
+            nbytes = 3 * h * w
+            if self.used + nbytes > self.budget:
+                return None
+            e = self.entries[path] = [self.used, h, w, False]
+            self.used = (self.used + nbytes + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+        return e
+
+    def filled(self, path):
+        e = self.entries.get(path)
+        return e is not None and e[3]
+
+    def fill(self, path, dev_img):
+        """Store the decoded image (uint8 [H, W, 3] on the device) in its reserved slot."""
+        off, h, w, _ = e = self.entries[path]
+        if tuple(dev_img.shape) != (h, w, 3):
+            raise RuntimeError(f"pggan_amd: {path} decodes to {tuple(dev_img.shape)}, its header "
+                               f"said {(h, w, 3)}")
+        self.buf[off:off + 3 * h * w].copy_(dev_img.reshape(-1), non_blocking=True)
+        e[3] = True
+
+
 def default_cache_bytes(device, fraction=0.4):
     """HBM for the image cache: `fraction` of the device's free memory now."""
     dev = torch.device(device)
@@ -135,14 +256,23 @@ class BatchLoader:
     flip + jitter + normalize on the GPU.  `next(indices, prefetch=None)` returns the fp32
     NCHW [-1, 1] batch on `device` and starts decoding `prefetch` (the next indices).
     cache_bytes > 0: decoded images are kept in an HbmImageCache and later batches gather
-    them there (no decode, no host-to-device copy); None: default_cache_bytes."""
+    them there (no decode, no host-to-device copy); None: default_cache_bytes.
+    source_cache: an HbmSourceCache shared by the loaders of every stage.  An image with a slot
+    there is decoded at most once per run, without the resize; its stage-size image comes from
+    `ops.resize_u8` straight into the batch (one call per distinct source shape), with the same
+    bytes as the host's PIL resize.  An image without room there takes the host path."""
 
-    def __init__(self, dataset, device, ops, seed=0, workers=None, gen=None, cache_bytes=None):
+    def __init__(self, dataset, device, ops, seed=0, workers=None, gen=None, cache_bytes=None,
+                 source_cache=None):
         """gen: the torch CPU generator the augmentation parameters are drawn from (shared
         across the loaders of successive stages); default a new one seeded with `seed`."""
         self.ds, self.dev, self.ops = dataset, torch.device(device), ops
         if not hasattr(ops, "augment_u8"):
             raise RuntimeError("pggan_amd: the input pipeline needs the HIP library (augment_u8)")
+        if source_cache is not None and not hasattr(ops, "resize_u8"):
+            raise RuntimeError("pggan_amd: the source cache needs the HIP library (resize_u8)")
+        self.src_cache = source_cache
+        self._rws = None
         self.pool = ThreadPoolExecutor(max_workers=workers or min(16, os.cpu_count() or 1))
         self.gen = gen if gen is not None else torch.Generator().manual_seed(seed)
         self._pending = {}       # dataset index -> future of its decoded image
@@ -167,10 +297,42 @@ class BatchLoader:
         return self.cache is not None and self.cache.slot[i] >= 0
 
     def _submit(self, idx):
+        """Start what index i still needs from the host: nothing (cached at this stage, or its
+        source is in HBM), the decode alone (a source slot to fill), or decode + resize."""
         for i in idx:
             i = int(i)
-            if i not in self._pending and not self._cached(i):
-                self._pending[i] = self.pool.submit(self.ds.load, i)
+            if i in self._pending or self._cached(i):
+                continue
+            if self.src_cache is not None:
+                path = self.ds.paths[i]
+                if self.src_cache.filled(path):
+                    continue
+                if self.src_cache.reserve(path) is not None:
+                    self._pending[i] = (True, self.pool.submit(self.ds.load_src, i))
+                    continue
+            self._pending[i] = (False, self.pool.submit(self.ds.load, i))
+
+    def _upload(self, arr):
+        t = torch.from_numpy(arr)
+        if self.dev.type == "cuda":
+            t = t.pin_memory()
+        return t.to(self.dev, non_blocking=True)
+
+    def _resize_from_source(self, rows, idx, src):
+        """Rows `rows` of the batch `src` [B, S, S, 3] from the source cache: one resize_u8
+        call per distinct source shape."""
+        S, sc = self.ds.size, self.src_cache
+        groups = {}
+        for k in rows:
+            off, h, w, _ = sc.entries[self.ds.paths[idx[k]]]
+            groups.setdefault((h, w), []).append((off, k * 3 * S * S))
+        for (h, w), offs in groups.items():
+            so = torch.tensor([o for o, _ in offs], dtype=torch.int64).to(self.dev)
+            do = torch.tensor([d for _, d in offs], dtype=torch.int64).to(self.dev)
+            self._rws = self.ops.resize_u8(sc.buf, so, h, w, S,
+                                           device_resize_coeffs(w, S, self.dev),
+                                           device_resize_coeffs(h, S, self.dev), src, do,
+                                           ws=self._rws)
 
     def next(self, idx, prefetch=None):
         if self._calls == 1:
@@ -182,13 +344,20 @@ class BatchLoader:
         miss = [k for k, i in enumerate(idx) if not self._cached(i)]
         src = torch.empty(B, S, S, 3, dtype=torch.uint8, device=self.dev)
         if miss:
-            imgs = [self._pending.pop(idx[k]).result() for k in miss]
-            self.decoded += len(imgs)
-            host = torch.from_numpy(np.stack(imgs)).pin_memory()
-            dev_miss = host.to(self.dev, non_blocking=True)
-            src[torch.tensor(miss, device=self.dev)] = dev_miss
+            got = {k: self._pending.pop(idx[k]) for k in miss if idx[k] in self._pending}
+            self.decoded += len(got)
+            for k, (is_src, fut) in got.items():        # decoded at source size: into its slot
+                if is_src and not self.src_cache.filled(self.ds.paths[idx[k]]):
+                    self.src_cache.fill(self.ds.paths[idx[k]], self._upload(fut.result()))
+            host_rows = [k for k, (is_src, _) in got.items() if not is_src]
+            gpu_rows = [k for k in miss if k not in host_rows]
+            if gpu_rows:
+                self._resize_from_source(gpu_rows, idx, src)
+            if host_rows:
+                dev_miss = self._upload(np.stack([got[k][1].result() for k in host_rows]))
+                src[torch.tensor(host_rows, device=self.dev)] = dev_miss
             if self.cache is not None:
-                self.cache.insert([idx[k] for k in miss], dev_miss)
+                self.cache.insert([idx[k] for k in miss], [src[k] for k in miss])
         hit = [k for k in range(B) if k not in miss]
         if hit:
             rows = torch.tensor([int(self.cache.slot[idx[k]]) for k in hit], device=self.dev)
@@ -204,7 +373,9 @@ class BatchLoader:
         return out
 
     def close(self):
-        """Stop the decode threads; pending prefetches are cancelled; the cache is freed."""
+        """Stop the decode threads; pending prefetches are cancelled; the stage's cache is
+        freed (a source cache stays with its owner; a slot reserved there for a cancelled
+        decode is filled by the next loader that asks for the image)."""
         self._pending = {}
         self.cache = None
         self.pool.shutdown(wait=False, cancel_futures=True)

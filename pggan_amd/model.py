@@ -33,7 +33,7 @@ import torch.distributed as dist
 from . import dp as DP
 from . import engine as E
 from .config import cfg_get
-from .data import BatchLoader, ImageFolderDataset
+from .data import BatchLoader, HbmSourceCache, ImageFolderDataset
 from .loss import WGANGPLoss
 from .nets import Discriminator, Generator
 
@@ -307,9 +307,16 @@ class ProgressiveGAN:
             # decoded images stay in HBM (pggan_amd.data.HbmImageCache): config
             # hbm_image_cache_gb, default 40 % of the free device memory
             gb = cfg_get(self.args, "hbm_image_cache_gb", None)
+            # hbm_source_cache_gb (opt-in): the decoded images at source size stay in HBM for
+            # the whole run (HbmSourceCache, this rank's shard), so a new stage's first epoch
+            # resizes them on the GPU instead of decoding every file again
+            sgb = float(cfg_get(self.args, "hbm_source_cache_gb", None) or 0)
+            if sgb > 0 and getattr(self, "_source_cache", None) is None:
+                self._source_cache = HbmSourceCache(self.device, int(sgb * (1 << 30)))
             self._loader = BatchLoader(self.train_dataset, self.device, _lib.HipOps(torch.float32),
                                        gen=self._aug_gen,
-                                       cache_bytes=None if gb is None else int(float(gb) * (1 << 30)))
+                                       cache_bytes=None if gb is None else int(float(gb) * (1 << 30)),
+                                       source_cache=getattr(self, "_source_cache", None))
         return self._loader.next(idx, prefetch=self._order[nxt:nxt + B])
 
     def set_loss_collector(self):
