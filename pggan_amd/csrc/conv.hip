@@ -1745,45 +1745,16 @@ int launch_tr(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
 // Which fused epilogues the kernel the dispatcher picks supports.
 template <typename T>
 bool conv_supported(const pg_conv_desc* d, size_t wsb) {
-  constexpr int BITS = PG_CONV_Y2_BITS | PG_CONV_AUX_BITS | PG_CONV_X_BITS;
-  if (d->flags & PG_CONV_RGBO) {   // the EF tiles 0 / 5 (16 / 32 channels), PixelNorm forward
-    if constexpr (sizeof(T) != 2) return false;
-    constexpr int PN = PG_CONV_PIXNORM | PG_CONV_LRELU | PG_CONV_BIAS;
-    if (d->flags != (PN | PG_CONV_RGBO) || !conv_hr_ok(d)) return false;
-    const int t = conv_hr_tile(d);
-    return (t == 0 && d->cout == 16) || (t == 5 && d->cout == 32);
+  if constexpr (sizeof(T) == 2) {
+    // conv_hr's shapes: some row of HR_ROWS runs these flags, with or without y2
+    if (conv_hr_ok(d)) return conv_hr_select(d, false) || conv_hr_select(d, true);
   }
-  if (d->flags & (PG_CONV_RGBW | PG_CONV_RGBD)) {   // the EF tiles 0 / 5 (16 / 32 channels)
-    if constexpr (sizeof(T) != 2) return false;
-    const int rf = d->flags & (PG_CONV_RGBW | PG_CONV_RGBD);
-    if (rf == (PG_CONV_RGBW | PG_CONV_RGBD)) return false;
-    if (d->flags != (rf | PG_CONV_MASK | PG_CONV_AUX_BITS) || !conv_hr_ok(d)) return false;
-    if ((d->flags & PG_CONV_RGBD) && d->B > 16) return false;
-    const int t = conv_hr_tile(d);
-    return (t == 0 && d->cout == 16) || (t == 5 && d->cout == 32);
-  }
-  if (d->flags & PG_CONV_PNBWD) {   // conv_hr epilogue, [cout][pixel] tiles of <= 32 channels
-    if constexpr (sizeof(T) != 2) return false;
-    if (d->flags & (BITS | PG_CONV_BIAS | PG_CONV_MASK | PG_CONV_ACCUM | PG_CONV_PIXNORM))
-      return false;
-    // after a 2x2 pool: the 32-channel tiles (their swap epilogue; y and r at pooled resolution)
-    if ((d->flags & PG_CONV_POOL) && (d->cout != 32 || conv_hr_bn(d) != 32)) return false;
-    return conv_hr_ok(d) && ((d->cout + 15) & ~15) <= conv_hr_bn(d) && conv_hr_bn(d) <= 32 &&
-           d->cout % 4 == 0;
-  }
-  if (d->flags & BITS) {
-    if constexpr (sizeof(T) != 2) return false;
-    if (!conv_hr_ok(d) || !conv_hr_mode_ok(d)) return false;
-    if ((d->flags & PG_CONV_PIXNORM) && ((d->cout + 15) & ~15) > conv_hr_bn(d)) return false;
-    return true;
-  }
+  // conv_lr and conv3x3_kernel: no RGB, PixelNorm-backward or sign-bit epilogues
+  if (d->flags & (PG_CONV_RGBO | PG_CONV_RGBW | PG_CONV_RGBD | PG_CONV_PNBWD | HR_BITS)) return false;
   if ((d->flags & PG_CONV_MASK) && (d->flags & PG_CONV_POOL)) return false;
   if (!(d->flags & PG_CONV_PIXNORM)) return true;
   if (d->flags & (PG_CONV_POOL | PG_CONV_MASK | PG_CONV_ACCUM)) return false;
   const int cout_p = (d->cout + 15) & ~15;
-  if constexpr (sizeof(T) == 2) {
-    if (conv_hr_ok(d)) return cout_p <= conv_hr_bn(d);
-  }
   int BM, BN;
   conv_tile_for(d->cout, &BM, &BN, d->W);
   const size_t need = conv_ws_bytes(d);
@@ -1795,11 +1766,13 @@ bool conv_supported(const pg_conv_desc* d, size_t wsb) {
 
 template <typename T>
 int conv_dispatch(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
+  if constexpr (sizeof(T) == 2) {
+    if (conv_hr_ok(d)) return conv_hr_dispatch(d, a, st);   // refuses what no row of HR_ROWS runs
+  }
   PG_CHECK_ARG(conv_supported<T>(d, a.ws_bytes), "conv3x3_fwd: flags 0x%x not supported for cout %d at %dx%d",
                d->flags, d->cout, d->H, d->W);
   if constexpr (sizeof(T) == 2) {
     if (conv_lr_ok(d)) return conv_lr_dispatch(d, a, st);
-    if (conv_hr_ok(d)) return conv_hr_dispatch(d, a, st);
   }
   int BM, BN;
   conv_tile_for(d->cout, &BM, &BN, d->W);
@@ -2075,7 +2048,10 @@ void plan_conv(int dtype, pg_conv_desc* d, int* path, int* tile, size_t* ws) {
   *tile = -1;
   if (dtype == PG_BF16) {
     if (conv_lr_ok(d)) { *path = 2; *ws = 0; return; }
-    if (conv_hr_ok(d)) { *path = 1; *tile = conv_hr_tile(d); *ws = 0; }
+    if (conv_hr_ok(d)) {
+      const HrRow* r = conv_hr_select(d, false);
+      *path = 1; *tile = r ? r->tile : -1; *ws = 0;
+    }
   }
 }
 }  // namespace

@@ -1688,52 +1688,274 @@ void conv_hr_kernel(ConvParams p) {
   }
 }
 
-// Host side: which convs take the fast path, and the launch.
-// tile 13 (8 x 16 pixels x 64 channels, LDS-DMA): the wide convs whose 16 x 16 tiles would
-// not fill the chip (32^2 at B = 4: 256 workgroups of 128 pixels; 2-7 % per launch against
-// conv3x3_kernel)
-bool conv_hr_t13(const pg_conv_desc* d) {
+// Host side.  HR_ROWS is the one list of conv_hr_kernel variants: a row is an instantiation
+// (nothing else is instantiated), its tile label and the rule by which conv_hr_select admits
+// a launch to it.  conv_supported, the step plan and conv_hr_dispatch all ask conv_hr_select,
+// so a new tile is a new row and nothing else.
+
+// sign-bit mode of a set of flags (at most one bit feature per launch)
+constexpr int hr_mode(int flags) {
+  if (flags & PG_CONV_X_BITS) return (flags & PG_CONV_AUX_BITS) ? HR_XAB : HR_XB;
+  if (flags & PG_CONV_Y2_BITS) return HR_YB;
+  if (flags & PG_CONV_AUX_BITS) return HR_AB;
+  return HR_PLAIN;
+}
+
+struct HrRow {
+  int tile;   // the label DESIGN.md, profiles/ and the step plan use
+  // conv_hr_kernel's template arguments
+  int CK, TH, BN;
+  bool PERSIST;
+  int NW, MODE, PD;
+  bool DB, DMA;
+  int EF;      // >= 0: the launch's flags (| HR_EF_Y2 with y2), matched exactly; -1: runtime flags
+  int takes;   // EF < 0: the flags a launch may carry (its sign-bit mode must be MODE)
+  int hmin;    // smallest H
+  bool (*geom)(const pg_conv_desc*);   // further geometry, or nullptr
+};
+
+constexpr int HR_BITS = PG_CONV_Y2_BITS | PG_CONV_AUX_BITS | PG_CONV_X_BITS;
+constexpr int HR_EPI = PG_CONV_UPS_IN | PG_CONV_BIAS | PG_CONV_LRELU | PG_CONV_MASK | PG_CONV_POOL |
+                       PG_CONV_ACCUM | PG_CONV_PIXNORM | HR_BITS;
+
+// a runtime-flag row; the PixelNorm backward epilogue is in the [cout][pixel] tiles of <= 32
+// channels.  Ring depth 1: the round-1 sweep measured it fastest for the runtime-flag persistent
+// variants (deeper rings cost occupancy)
+constexpr HrRow hr_rt(int tile, int CK, int TH, int BN, bool persist, int NW, int mode, bool DB = false,
+                      bool DMA = false, bool (*geom)(const pg_conv_desc*) = nullptr) {
+  return {tile, CK, TH, BN, persist, NW, mode, 1, DB, DMA, -1, HR_EPI | (BN <= 32 ? PG_CONV_PNBWD : 0),
+          16, geom};
+}
+// a persistent row with its flags fixed at compile time (EF, see conv_hr_kernel), as the engine
+// issues them at 128^2 .. 1024^2
+constexpr HrRow hr_ef(int tile, int CK, int TH, int BN, int NW, int PD, int hmin, int ef) {
+  return {tile, CK, TH, BN, true, NW, hr_mode(ef), PD, false, false, ef, 0, hmin, nullptr};
+}
+
+// tile 13: the wide convs whose 16 x 16 tiles would not fill the chip (32^2 at B = 4: 256
+// workgroups of 128 pixels)
+bool hr_geom_t13(const pg_conv_desc* d) {
   const size_t px = (size_t)d->B * d->H * d->W;
   // where the 16-row tiles (tile 6) already give 256 workgroups with the 64-channel blocks
   // counted, they take the launch: 32^2 512 -> 512 at B = 8 (the merged passes) 55.4 -> 45.7 us
   // per launch, 128 vs 256 KiB of staging per output pixel block (profiles/r5_lowres_tiles.txt)
   if (px / 256 * (((d->cout + 15) & ~15) / 64) >= 256) return false;
-  return d->cout > 64 && px / 256 < 64 && px / 128 >= 32 && cinp_of(d->cin) % 32 == 0 &&
-         d->H % 8 == 0 && ((d->H / 8) & (d->H / 8 - 1)) == 0 &&
-         !(d->flags & (PG_CONV_Y2_BITS | PG_CONV_AUX_BITS | PG_CONV_X_BITS | PG_CONV_PIXNORM |
-                       PG_CONV_PNBWD));
+  return d->cout > 64 && px / 256 < 64 && px / 128 >= 32;
+}
+// tile 3: 32-row tiles when they still give a workgroup per CU
+bool hr_geom_t3(const pg_conv_desc* d) {
+  return (long)d->B * (d->W / 16) * (d->H / 32) * pg_cdiv((d->cout + 15) & ~15, 64) >= 256;
 }
 
+constexpr int HR_Y = HR_EF_Y2;
+constexpr int HR_PN = PG_CONV_PIXNORM | PG_CONV_LRELU | PG_CONV_BIAS;
+constexpr int HR_LB = PG_CONV_LRELU | PG_CONV_BIAS;
+constexpr int HR_AM = PG_CONV_AUX_BITS | PG_CONV_MASK;
+constexpr int HR_XM = PG_CONV_X_BITS | PG_CONV_MASK | PG_CONV_UPS_IN;
+
+// In the order of preference: tiles 13 - 16, then by channel counts (the tile sweeps of rounds
+// 1 - 4 chose these; tiles measured slower were removed); an EF row before its tile's
+// runtime-flag rows, which take what no EF row matches.  Tiles 14 - 16 have EF rows only: what
+// those do not match goes on to tiles 3 / 6 / 8.
+constexpr HrRow HR_ROWS[] = {
+    // tile 13 (8 x 16 pixels x 64 channels, LDS-DMA, two LDS slots): the wide convs at 32^2,
+    // 2-7 % per launch against conv3x3_kernel.  Not in the asm-DMA form (+8-11 % per launch,
+    // profiles/r6_t13_adma_ab.txt)
+    {13, 32, 8, 64, false, 4, HR_PLAIN, 1, false, true, -1, HR_EPI & ~PG_CONV_PIXNORM, 16, hr_geom_t13},
+
+#define T14(EF) hr_ef(14, 32, 16, 64, 8, 2, 256, EF)
+    // tile 14: the 32 -> 64 sign-bit convs of the discriminator's 512^2 level (conv b forward
+    // with Y2_BITS, R1 tangent with AUX_BITS).  One 32-channel chunk per tile: tile 3 ran each
+    // workgroup's single DMA, MFMAs and epilogue back to back with one workgroup per CU (nothing
+    // overlapped, ~85 us); the persistent form keeps the weight slab in LDS and the next tiles'
+    // halos in flight (kbench 90.6 -> 74.0 us, profiles/r4_t14ef_ab.txt).  8 waves (two per SIMD
+    // per workgroup, two workgroups per CU) against 4: 74.1 -> 56.4 us (forward), 64.8 -> 53.5
+    // (tangent) at B = 4, 142.5 -> 106.1 / 128.3 -> 110.2 at B = 8 (profiles/r6_ef_waves_ab.txt).
+    // (PG_CONV_POOL alone -- the generator's 512^2 pooled input gradient -- measured the same as
+    // tile 3: 72.5 vs 72.6 us, profiles/r4_bits_kbench.txt: no row)
+    T14(PG_CONV_Y2_BITS | PG_CONV_POOL | HR_LB | HR_Y), T14(HR_AM | PG_CONV_POOL),
+#undef T14
+
+#define T15(EF) hr_ef(15, 64, 8, 32, 4, 2, 256, EF)
+    // tile 15: 64 -> 32 at >= 256^2 with the whole 64-channel K in one chunk: the G conv a
+    // forward (up2 input, PixelNorm epilogue) and the D conv-b input gradient (X_BITS, also with
+    // the AUX_BITS mask) of the 512^2 level.  Tile 8 (CK = 32, two chunks, one tile per workgroup,
+    // runtime flags) ran them at 1.5-2.4 TB/s.  8-row tiles (two workgroups per CU: 67 KiB of LDS)
+    // beat 16-row ones (one per CU): at B = 8 158 / 170 us (tile 8) -> 138 / 133 (TH 16) -> 104 /
+    // 107 (TH 8); at B = 4 79 / 77 -> 56 / 55 (profiles/r5_t15_ab.txt)
+    T15(HR_PN | PG_CONV_UPS_IN), T15(HR_PN | PG_CONV_UPS_IN | HR_Y), T15(HR_XM),
+    T15(HR_XM | PG_CONV_AUX_BITS),
+#undef T15
+
+#define T16(EF) hr_ef(16, 64, 16, 64, 8, 2, 128, EF)
+    // tile 16: 64 -> 64 at >= 128^2 (the 256^2 level: D conv a, G conv b; forward, input
+    // gradient, tangent) with the whole 64-channel K in one chunk: the 64 x 9 x 64 weight slab
+    // stays in LDS and each workgroup walks its tiles with the next halos in flight.  Tile 3
+    // (32-channel chunks, one tile per workgroup, one workgroup per CU) re-read the slab per tile
+    // and exposed each tile's first DMA and epilogue
+    T16(0), T16(HR_LB), T16(PG_CONV_MASK), T16(HR_PN), T16(HR_PN | HR_Y),
+#undef T16
+
+    // The narrow EF tiles 0, 1, 4, 5 (16 / 32 channels at 512^2 / 1024^2).  8 waves against 4:
+    // per launch -5 .. +7 % by shape in isolation, the whole step 9.983 -> 9.889 ms in 3 of 3
+    // interleaved rounds (more waves per SIMD beside the side stream's weight gradients).
+    // Ring depth 2: with depth 1 the loop entry (the first halo the youngest load) and the back
+    // edge (the previous tile's stores younger than it) disagree, and the compiler's counting
+    // falls back to vmcnt(0) at every halo store; at depth 2 the other slot's loads are younger
+    // on both paths (checked in the ISA: no vmcnt(0) in the loop).  Depth 1 is still faster for
+    // tiles 1 and 4 (kbench 116 -> 64 / 92 -> 87 us vs 79 / 95 at depth 2: their larger epilogue
+    // covers the halo latency); depth 4 measured slower (profiles/r6_tile3_alternatives.txt).
+    // A launch whose tile count is no multiple of the depth takes the runtime-flag row.
+#define T0(EF) hr_ef(0, 16, 16, 16, 8, 2, 16, EF)
+    // tile 0: 16 -> 16 (1024^2: D conv a fwd / dgrad / tangent, G conv b fwd / dgrad)
+    T0(0), T0(HR_LB), T0(PG_CONV_MASK), T0(HR_PN), T0(HR_PN | HR_Y),
+    // ... with the toRGB output in the epilogue (the generator's top conv b, alpha = 1)
+    T0(HR_PN | PG_CONV_RGBO), T0(HR_PN | HR_Y | PG_CONV_RGBO),
+    T0(PG_CONV_PNBWD | HR_Y),
+    // conv a forward with the sign bits of its activation; its lrelu' consumers from those bits
+    // (unpooled Y2_BITS / AUX_BITS exist only as these rows and tile 5's)
+    T0(PG_CONV_Y2_BITS | HR_LB | HR_Y), T0(HR_AM),
+    // ... with the fromRGB weight gradient in the epilogue (the final backward pass)
+    T0(HR_AM | PG_CONV_RGBW),
+    // ... with the fromRGB input gradient (the penalty's and the G half's passes)
+    T0(HR_AM | PG_CONV_RGBD),
+#undef T0
+    hr_rt(0, 16, 16, 16, true, 4, HR_PLAIN),
+
+#define T1(EF) hr_ef(1, 16, 16, 32, 8, 1, 16, EF)
+    // tile 1: 16 -> 32 (1024^2: D conv b fwd (sign bits) / tangent, G conv a dgrad)
+    T1(PG_CONV_Y2_BITS | PG_CONV_POOL | HR_LB | HR_Y), T1(HR_AM | PG_CONV_POOL),
+    T1(PG_CONV_POOL), T1(PG_CONV_POOL | PG_CONV_ACCUM),
+    // the G conv-a input gradient at 1024^2 with the 512^2 block's PixelNorm backward after the pool
+    T1(PG_CONV_POOL | PG_CONV_PNBWD | HR_Y),
+#undef T1
+    hr_rt(1, 16, 16, 32, true, 4, HR_PLAIN), hr_rt(1, 16, 16, 32, true, 4, HR_YB),
+    hr_rt(1, 16, 16, 32, true, 4, HR_AB),
+
+    hr_rt(2, 16, 16, 64, false, 4, HR_PLAIN),
+
+    // tile 3 (32 x 16 pixels x 64 channels): the wide convs at 64^2 - 256^2 and D conv b forward
+    // / tangent there (Y2_BITS / AUX_BITS), LDS-DMA double-buffered staging in the inline-asm
+    // form (overlapped staging, masks after the loop: A/B 298.0 -> 305.3 img/s, 5-7 % per launch).
+    // 16 waves (2 x 4 blocks per wave, four waves per SIMD, 64 VGPRs) against 8 (4 x 4, two per
+    // SIMD): 128^2 128 -> 128 24.0 -> 22.9 us at B = 4, 45.3 -> 42.6 at B = 8, 128 -> 256 pooled
+    // 85.8 -> 84.5, step 10.249 -> 10.160 ms; the sign-bit modes -4 .. -17 % per launch, step
+    // 10.270 -> 10.217 ms (profiles/r6_t3_waves_ab.txt).  (Instantiated in this order hipcc
+    // emits the code that was measured; with the plain row first two of the three come out
+    // some 60 bytes different.)
+    hr_rt(3, 32, 32, 64, false, 16, HR_YB, true, true, hr_geom_t3),
+    hr_rt(3, 32, 32, 64, false, 16, HR_AB, true, true, hr_geom_t3),
+    hr_rt(3, 32, 32, 64, false, 16, HR_PLAIN, true, true, hr_geom_t3),
+
+#define T4(EF) hr_ef(4, 32, 16, 16, 8, 1, 16, EF)
+    // tile 4: 32 -> 16 (1024^2: D conv b dgrad with sign bits, G conv a fwd)
+    T4(HR_XM), T4(HR_XM | PG_CONV_AUX_BITS), T4(HR_PN | PG_CONV_UPS_IN),
+    T4(HR_PN | PG_CONV_UPS_IN | HR_Y),
+#undef T4
+    hr_rt(4, 32, 16, 16, true, 4, HR_PLAIN), hr_rt(4, 32, 16, 16, true, 4, HR_XB),
+    hr_rt(4, 32, 16, 16, true, 4, HR_XAB),
+
+#define T5(EF) hr_ef(5, 32, 16, 32, 8, 2, 16, EF)
+    // tile 5: 32 -> 32 (512^2: D conv a, G conv b), the same launches as tile 0
+    T5(0), T5(HR_LB), T5(PG_CONV_MASK), T5(HR_PN), T5(HR_PN | HR_Y),
+    T5(HR_PN | PG_CONV_RGBO), T5(HR_PN | HR_Y | PG_CONV_RGBO),
+    T5(PG_CONV_PNBWD | HR_Y),
+    T5(PG_CONV_Y2_BITS | HR_LB | HR_Y), T5(HR_AM),
+    T5(HR_AM | PG_CONV_RGBW),
+    T5(HR_AM | PG_CONV_RGBD),
+#undef T5
+    hr_rt(5, 32, 16, 32, true, 4, HR_PLAIN), hr_rt(5, 32, 16, 32, true, 4, HR_XB),
+    hr_rt(5, 32, 16, 32, true, 4, HR_XAB),
+
+    // tile 6 (16 x 16 pixels x 64 channels): tile 3's asm-DMA form on 16-row tiles.  8 waves (two
+    // per SIMD) against 4: 64^2 256 -> 256 29.0 -> 24.0 us, 512 -> 256 48.8 -> 41.9 at B = 4,
+    // 32^2 512 -> 512 48.5 -> 41.1 at B = 8; step 9.675 -> 9.614 ms (profiles/r6_t6_waves_ab.txt)
+    hr_rt(6, 32, 16, 64, false, 8, HR_PLAIN, true, true),
+
+    // tiles 7, 8: more than one 32-channel chunk into 16 / 32 channels, one tile per workgroup
+    hr_rt(7, 32, 16, 16, false, 4, HR_PLAIN),
+    hr_rt(8, 32, 16, 32, false, 4, HR_PLAIN), hr_rt(8, 32, 16, 32, false, 4, HR_XB),
+    hr_rt(8, 32, 16, 32, false, 4, HR_XAB),
+};
+constexpr int HR_NROWS = sizeof(HR_ROWS) / sizeof(HR_ROWS[0]);
+static_assert(HR_ROWS[0].tile == 13, "conv_hr_ok reads tile 13's row");
+
+// Whether row r runs this launch (ef = its flags, | HR_EF_Y2 with y2): the flags, then the
+// geometry, then what launch_conv_hr asserts of the row
+bool hr_admits(const HrRow& r, const pg_conv_desc* d, int ef) {
+  if (r.EF >= 0 ? ef != r.EF || d->cout != r.BN
+                : (d->flags & ~r.takes) || hr_mode(d->flags) != r.MODE)
+    return false;
+  const int cin_p = cinp_of(d->cin), cout_p = (d->cout + 15) & ~15;
+  // every variant is [cout][pixel]: the narrowest of 16 / 32 / 64 channels that holds cout,
+  // wider outputs in blocks of 64; PixelNorm (and its backward) needs a pixel's channels in one
+  if (r.BN != (cout_p <= 16 ? 16 : cout_p <= 32 ? 32 : 64)) return false;
+  if ((d->flags & (PG_CONV_PIXNORM | PG_CONV_PNBWD)) && cout_p > r.BN) return false;
+  // persistent rows and the 16-channel chunk hold all of K; the others walk 32-channel chunks
+  if ((r.PERSIST || r.CK == 16) ? cin_p != r.CK : cin_p % r.CK != 0) return false;
+  const int tx = d->W / 16, ty = d->H / r.TH;
+  if (d->H < r.hmin || d->H % r.TH || (tx & (tx - 1)) || (ty & (ty - 1))) return false;
+  if (r.geom && !r.geom(d)) return false;
+  // the EXACT grid: every workgroup walks a multiple of the ring depth
+  if (r.EF >= 0 && (d->B * tx * ty) % r.PD) return false;
+  if (r.EF >= 0 && (r.EF & PG_CONV_RGBD) && d->B > 16) return false;
+  if (r.DMA) {   // one buffer resource over the whole input, see launch_conv_hr
+    const int ups = d->flags & PG_CONV_UPS_IN ? 2 : 1;
+    if ((size_t)d->B * (d->H / ups) * (d->W / ups) * std::max(d->x_cs, cin_p) * 2 > 0x7fff0000ull)
+      return false;
+  }
+  return true;
+}
+
+// The shapes of this path (a conv it holds never falls back to conv3x3_kernel)
 bool conv_hr_ok(const pg_conv_desc* d) {
   const int cin_p = cinp_of(d->cin);
   if (d->W < 16 || d->H < 16 || (d->W & 15) || d->B <= 0) return false;
   if (cin_p != 16 && cin_p % 32 != 0) return false;
-  if (d->cout > 64) {
-    // wide outputs only where the 16 x 16 tiles x 64-channel blocks fill the chip (or tile 13
-    // does)
-    if ((size_t)d->B * d->H * d->W / 256 * (((d->cout + 15) & ~15) / 64) < 256 && !conv_hr_t13(d)) return false;
-  }
-  // MASK with POOL only from sign bits (mask before the pool)
-  if ((d->flags & PG_CONV_MASK) && (d->flags & PG_CONV_POOL) && !(d->flags & PG_CONV_AUX_BITS))
-    return false;
-  if ((d->flags & PG_CONV_POOL) && (d->H & 1)) return false;
-  if ((d->flags & (PG_CONV_Y2_BITS | PG_CONV_AUX_BITS)) && (d->cout & 15)) return false;
-  // Y2_BITS without the pool: the sign bits of a 16 / 32-channel activation (tiles 0, 5)
-  if ((d->flags & PG_CONV_Y2_BITS) && !(d->flags & PG_CONV_POOL) &&
-      (cin_p > 32 || (d->cout != 16 && d->cout != 32)))
-    return false;
+  // wide outputs only where the 16 x 16 tiles x 64-channel blocks fill the chip, or tile 13 runs
+  if (d->cout > 64 && (size_t)d->B * d->H * d->W / 256 * (((d->cout + 15) & ~15) / 64) < 256)
+    return hr_admits(HR_ROWS[0], d, d->flags);
   return true;
 }
 
-// the output-channel tile conv_hr_dispatch picks (every variant is [cout][pixel])
-int conv_hr_bn(const pg_conv_desc* d) {
-  const int cout_p = (d->cout + 15) & ~15;
-  return cout_p <= 16 ? 16 : cout_p <= 32 ? 32 : 64;
+// The variant that runs a conv, or nullptr: a pure function of the descriptor and of whether y2
+// is given.  A stride the descriptor leaves 0 (a support query) counts as the smallest valid one.
+const HrRow* conv_hr_select(const pg_conv_desc* d, bool y2) {
+  if (!conv_hr_ok(d)) return nullptr;
+  const int f = d->flags, cin_p = cinp_of(d->cin);
+  // MASK with POOL only from sign bits (mask before the pool)
+  if ((f & PG_CONV_MASK) && (f & PG_CONV_POOL) && !(f & PG_CONV_AUX_BITS)) return nullptr;
+  if ((f & (PG_CONV_Y2_BITS | PG_CONV_AUX_BITS)) && (d->cout & 15)) return nullptr;
+  // Y2_BITS without the pool: the sign bits of a 16 / 32-channel activation
+  if ((f & PG_CONV_Y2_BITS) && !(f & PG_CONV_POOL) && (cin_p > 32 || (d->cout != 16 && d->cout != 32)))
+    return nullptr;
+  // X_BITS is staged at half resolution
+  if ((f & PG_CONV_X_BITS) && !(f & PG_CONV_UPS_IN)) return nullptr;
+  if (f & PG_CONV_PNBWD) {
+    if (f & (HR_BITS | PG_CONV_BIAS | PG_CONV_MASK | PG_CONV_ACCUM | PG_CONV_PIXNORM)) return nullptr;
+    // after a 2x2 pool: the 32-channel tiles (their swap epilogue; y and r at pooled resolution)
+    if (((f & PG_CONV_POOL) && d->cout != 32) || d->cout % 4) return nullptr;
+  } else if ((f & PG_CONV_PIXNORM) && !(f & HR_BITS) && (f & (PG_CONV_POOL | PG_CONV_MASK | PG_CONV_ACCUM))) {
+    return nullptr;
+  }
+  {  // the kernel addresses inside one image with 32-bit element offsets
+    const size_t cs = std::max({d->x_cs, cin_p, d->y_cs, d->cout, d->aux_cs, d->y2_cs, d->xb_cs});
+    if ((size_t)d->H * d->W * (cs + 16) >= (1ull << 31)) return nullptr;
+  }
+  const int ef = f | (y2 ? HR_EF_Y2 : 0);
+  for (const HrRow& r : HR_ROWS)
+    if (hr_admits(r, d, ef)) return &r;
+  return nullptr;
 }
 
-template <int CK, int TH, int BN, bool PERSIST, int NWAVES = 4, int MODE = HR_PLAIN, int PD = 1,
-          bool DB = false, bool DMA = false, int EF = -1>
+// Launches row I.  The PG_CHECK_ARGs up to the first HIP call assert what conv_hr_select
+// promised of the row and check the operands it cannot see.
+template <int I>
 int launch_conv_hr(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
+  constexpr HrRow R = HR_ROWS[I];
+  constexpr int CK = R.CK, TH = R.TH, BN = R.BN, NWAVES = R.NW, MODE = R.MODE, PD = R.PD, EF = R.EF;
+  constexpr bool PERSIST = R.PERSIST, DB = R.DB, DMA = R.DMA;
+  constexpr auto kernel = conv_hr_kernel<CK, TH, BN, PERSIST, NWAVES, MODE, PD, DB, DMA, EF>;
   constexpr int KS = (9 * CK + 31) / 32;
   constexpr int PIXB = CK * 2 + (CK * 2 >= 64 ? 32 : 0);
   constexpr int HALO_BYTES = ((TH + 2) * 18 * PIXB + 15) & ~15;
@@ -1780,25 +2002,25 @@ int launch_conv_hr(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
   PG_CHECK_ARG(!DMA || (size_t)d->B * p.Hin * p.Win * d->x_cs * 2 <= 0x7fff0000ull,
                "conv_hr: input too large for the LDS-DMA tiles");
   const int ntiles = d->B * (d->W / 16) * (d->H / TH);
+  // EXACT: every workgroup walks ntiles / grid tiles, a multiple of PD
+  PG_CHECK_ARG(EF < 0 || ntiles % PD == 0, "conv_hr: EF needs ntiles %% PD == 0");
   // the launch's own size (not 160 KiB: the RGBW variants also hold det_commit's static word)
-  PG_LDS_ATTR((conv_hr_kernel<CK, TH, BN, PERSIST, NWAVES, MODE, PD, DB, DMA, EF>), LDS);
+  PG_LDS_ATTR(kernel, LDS);
   dim3 grid;
   if (PERSIST) {
     // one resident wave of workgroups (occupancy of this variant x 256 CUs): a larger
     // grid runs as two serial rounds of persistent workgroups
     static int per_cu = 0;
     if (!per_cu) {
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(
-          &per_cu, (const void*)conv_hr_kernel<CK, TH, BN, PERSIST, NWAVES, MODE, PD, DB, DMA, EF>, NWAVES * 64, LDS);
+      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kernel, NWAVES * 64, LDS);
       if (per_cu < 1) per_cu = 1;
       if (per_cu > 8) per_cu = 8;
     }
     int g = 256 * per_cu;
-    if (EF >= 0) {   // EXACT: every workgroup walks ntiles / g tiles, a multiple of PD
+    if (EF >= 0) {   // the largest power of two <= g that divides ntiles / PD
       int gp = 1;
       while (gp * 2 <= g && (ntiles / PD) % (gp * 2) == 0) gp *= 2;
       g = gp;
-      PG_CHECK_ARG(ntiles % (PD * g) == 0, "conv_hr: EF needs ntiles %% (PD * grid) == 0");
     }
     grid = dim3(ntiles < g ? ntiles : g, 1, 1);
   } else {
@@ -1806,282 +2028,23 @@ int launch_conv_hr(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
     grid = dim3(ntiles, cb, 1);
     p.tpw = 1;
   }
-  PG_KLAUNCH((conv_hr_kernel<CK, TH, BN, PERSIST, NWAVES, MODE, PD, DB, DMA, EF>), grid, dim3(NWAVES * 64), LDS,
-                     st, p);
+  PG_KLAUNCH(kernel, grid, dim3(NWAVES * 64), LDS, st, p);
   PG_LAUNCH_CHECK();
   return PG_OK;
 }
 
-// sign-bit mode of a launch (at most one bit feature per launch)
-int conv_hr_mode(const pg_conv_desc* d) {
-  if (d->flags & PG_CONV_X_BITS) return (d->flags & PG_CONV_AUX_BITS) ? HR_XAB : HR_XB;
-  if (d->flags & PG_CONV_Y2_BITS) return HR_YB;
-  if (d->flags & PG_CONV_AUX_BITS) return HR_AB;
-  return HR_PLAIN;
-}
-
-// tile 14 with compile-time flags (EF): the 32 -> 64 sign-bit convs of the discriminator's
-// 512^2 level (conv b forward with Y2_BITS, R1 tangent with AUX_BITS).  One 32-channel chunk
-// per tile: tile 3 ran each workgroup's single DMA, MFMAs and epilogue back to back with one
-// workgroup per CU (nothing overlapped, ~85 us); the persistent form keeps the weight slab in
-// LDS and the next tiles' halos in flight (kbench 90.6 -> 74.0 us, profiles/r4_t14ef_ab.txt)
-bool conv_hr_t14ef(const pg_conv_desc* d) {
-  constexpr int YBF = PG_CONV_BIAS | PG_CONV_LRELU | PG_CONV_POOL | PG_CONV_Y2_BITS;
-  constexpr int ABF = PG_CONV_MASK | PG_CONV_AUX_BITS | PG_CONV_POOL;
-  // (PG_CONV_POOL alone -- the generator's 512^2 pooled input gradient -- measured the same as
-  // tile 3: 72.5 vs 72.6 us, profiles/r4_bits_kbench.txt)
-  return cinp_of(d->cin) == 32 && d->cout == 64 && d->H >= 256 && d->H % 16 == 0 &&
-         (d->flags == YBF || d->flags == ABF);
-}
-
-#ifndef PG_T15_TH
-#define PG_T15_TH 8
-#endif
-// tile 15: 64 -> 32 at >= 256^2 with the whole 64-channel K in one chunk (CK = 64), persistent
-// with compile-time flags: the G conv a forward (up2 input, PixelNorm epilogue) and the D conv-b
-// input gradient (X_BITS, also with the AUX_BITS mask) of the 512^2 level.  Tile 8 (CK = 32,
-// two chunks, one tile per workgroup, runtime flags) ran them at 1.5-2.4 TB/s.  8-row tiles (two
-// workgroups per CU: 67 KiB of LDS) beat 16-row ones (one per CU): at B = 8 158 / 170 us (tile 8)
-// -> 138 / 133 (TH 16) -> 104 / 107 (TH 8); at B = 4 79 / 77 -> 56 / 55 (profiles/r5_t15_ab.txt)
-bool conv_hr_t15ef(const pg_conv_desc* d) {
-  constexpr int PNU = PG_CONV_PIXNORM | PG_CONV_LRELU | PG_CONV_BIAS | PG_CONV_UPS_IN;
-  constexpr int XB = PG_CONV_X_BITS | PG_CONV_MASK | PG_CONV_UPS_IN;
-  return cinp_of(d->cin) == 64 && d->cout == 32 && d->H >= 256 && d->H % 16 == 0 &&
-         (d->flags == PNU || d->flags == XB || d->flags == (XB | PG_CONV_AUX_BITS));
-}
-
-#ifndef PG_T16_TH
-#define PG_T16_TH 16
-#endif
-#ifndef PG_T16_NW
-#define PG_T16_NW 8
-#endif
-// tile 16: 64 -> 64 at >= 128^2 (the 256^2 level: D conv a, G conv b and their input
-// gradients), persistent with the whole 64-channel K in one chunk and compile-time flags: the
-// 64 x 9 x 64 weight slab stays in LDS and each workgroup walks its tiles with the next halos
-// in flight.  Tile 3 (32-channel chunks, one tile per workgroup, one workgroup per CU) re-read
-// the slab per tile and exposed each tile's first DMA and epilogue.
-bool conv_hr_t16ef(const pg_conv_desc* d) {
-  constexpr int PN = PG_CONV_PIXNORM | PG_CONV_LRELU | PG_CONV_BIAS;
-  return cinp_of(d->cin) == 64 && d->cout == 64 && d->H >= 128 && d->H % 16 == 0 &&
-         (d->flags == 0 || d->flags == (PG_CONV_LRELU | PG_CONV_BIAS) || d->flags == PG_CONV_MASK ||
-          d->flags == PN);
-}
-
-// The tile conv_hr_dispatch picks (the tile sweeps of rounds 1-4 chose these; tiles measured
-// slower were removed)
-int conv_hr_tile(const pg_conv_desc* d) {
-  const int cin_p = cinp_of(d->cin);
-  const int cout_p = (d->cout + 15) & ~15;
-  if (conv_hr_t13(d)) return 13;
-  if (conv_hr_t14ef(d)) return 14;
-  if (conv_hr_t15ef(d)) return 15;
-  if (conv_hr_t16ef(d)) return 16;
-  if (cin_p == 16) return cout_p <= 16 ? 0 : cout_p <= 32 ? 1 : 2;
-  if (cout_p > 32 && d->H % 32 == 0 &&
-      (long)d->B * (d->W / 16) * (d->H / 32) * pg_cdiv(cout_p, 64) >= 256)
-    return 3;
-  if (cin_p == 32) return cout_p <= 16 ? 4 : cout_p <= 32 ? 5 : 6;
-  return cout_p <= 16 ? 7 : cout_p <= 32 ? 8 : 6;
-}
-
-// sign-bit modes are instantiated only for the tiles of the layers that use them (the
-// discriminator's top two levels, see engine._dbits): (tile, mode) pairs below
-bool conv_hr_mode_ok(const pg_conv_desc* d) {
-  const int m = conv_hr_mode(d);
-  if (m == HR_PLAIN) return true;
-  const int t = conv_hr_tile(d);
-  if (m == HR_XB || m == HR_XAB) return t == 4 || t == 8 || t == 5 || t == 15;
-  // HR_YB, HR_AB: conv b forward / tangent at 1024^2, 512^2 (pooled: tiles 1, 3, 14); conv a
-  // forward / tangent / input gradient at 1024^2, 512^2 (unpooled, compile-time flags: 0, 5)
-  if (!(d->flags & PG_CONV_POOL) && (t == 0 || t == 5)) return true;
-  return t == 1 || t == 3 || t == 14;
-}
-
-// ring depth 1 for the runtime-flag persistent variants (the round-1 sweep measured depth 1
-// fastest: deeper rings cost occupancy)
-template <int CK, int TH, int BN, bool PERSIST, int NW, int MODE>
-int launch_hr_pd(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
-  return launch_conv_hr<CK, TH, BN, PERSIST, NW, MODE, 1>(d, a, st);
-}
-
-// waves of tile 3 (plain mode): 16 (2 x 4 blocks per wave, four waves per SIMD, 64 VGPRs)
-// against 8 (4 x 4, two per SIMD): 128^2 128 -> 128 24.0 -> 22.9 us at B = 4, 45.3 -> 42.6 at
-// B = 8, 128 -> 256 pooled 85.8 -> 84.5; step 10.249 -> 10.160 ms (profiles/r6_t3_waves_ab.txt)
-#ifndef PG_T3_NW
-#define PG_T3_NW 16
-#endif
-// waves of tile 3's sign-bit modes (Y2_BITS / AUX_BITS: D conv b forward / tangent at 64^2-256^2):
-// 16 against 8: -4 .. -17 % per launch, step 10.270 -> 10.217 ms (profiles/r6_t3_waves_ab.txt)
-#ifndef PG_T3B_NW
-#define PG_T3B_NW 16
-#endif
-// waves of tile 6 (the 16-row LDS-DMA wide tile): 8 (tile 3's asm-DMA form on 16-row tiles, two
-// waves per SIMD) against 4 (one): 64^2 256 -> 256 29.0 -> 24.0 us, 512 -> 256 48.8 -> 41.9 at
-// B = 4, 32^2 512 -> 512 48.5 -> 41.1 at B = 8; step 9.675 -> 9.614 ms (profiles/r6_t6_waves_ab.txt)
-#ifndef PG_T6_NW
-#define PG_T6_NW 8
-#endif
-// waves of tile 14 (the 512^2 32 -> 64 sign-bit convs): 8 (two per SIMD per workgroup, two
-// workgroups per CU) against 4: 74.1 -> 56.4 us (Y2_BITS forward), 64.8 -> 53.5 (tangent) at
-// B = 4, 142.5 -> 106.1 / 128.3 -> 110.2 at B = 8 (profiles/r6_ef_waves_ab.txt)
-#ifndef PG_T14_NW
-#define PG_T14_NW 8
-#endif
-// waves of the narrow EF tiles 0, 1, 4, 5 (16 / 32 channels at 512^2 / 1024^2): 8 against 4
-// per launch -5 .. +7 % by shape in isolation, the whole step 9.983 -> 9.889 ms in 3 of 3
-// interleaved rounds (more waves per SIMD beside the side stream's weight gradients)
-#ifndef PG_EF_NW
-#define PG_EF_NW 8
-#endif
-// halo ring depth of the EF tiles that do not take depth 1 (a power of two: the EXACT grid
-// divides the tile count by depth x grid)
-#ifndef PG_HR_EF_PD
-#define PG_HR_EF_PD 2
-#endif
-template <int CK, int TH, int BN, int MODE, int EF, int NW = 4>
-int launch_hr_ef(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
-  if constexpr (NW != 4) {
-    constexpr int PDv = ((CK == 32 && BN == 16) || (CK == 16 && BN == 32)) ? 1 : PG_HR_EF_PD;
-    return launch_conv_hr<CK, TH, BN, true, NW, MODE, PDv, false, false, EF>(d, a, st);
-  }
-  // ring depth 2 by default: with depth 1 the loop entry (the first halo the youngest load)
-  // and the back edge (the previous tile's stores younger than it) disagree, and the
-  // compiler's counting falls back to vmcnt(0) at every halo store; at depth 2 the other
-  // slot's loads are younger on both paths (checked in the ISA: no vmcnt(0) in the loop)
-  // (kbench: depth 1 is still faster for the 16 -> 32 pooled and 32 -> 16 tiles, 116 -> 64 /
-  // 92 -> 87 us vs 79 / 95 at depth 2: their larger epilogue covers the halo latency)
-  if ((CK == 32 && BN == 16) || (CK == 16 && BN == 32))
-    return launch_conv_hr<CK, TH, BN, true, 4, MODE, 1, false, false, EF>(d, a, st);
-  return launch_conv_hr<CK, TH, BN, true, 4, MODE, PG_HR_EF_PD, false, false, EF>(d, a, st);
-}
-
-// The persistent narrow launches of the training step with their flags fixed at compile
-// time (EF, see conv_hr_kernel): (tile, mode, flags | HR_EF_Y2 if y2) as the engine issues
-// them at 512^2 / 1024^2.  Returns PG_ERR_UNSUPPORTED for anything else (runtime-flag form).
-int conv_hr_ef_dispatch(int tile, int m, const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
-  const int ef = d->flags | (a.y2 ? HR_EF_Y2 : 0);
-  constexpr int Y = HR_EF_Y2;
-  constexpr int PN = PG_CONV_PIXNORM | PG_CONV_LRELU | PG_CONV_BIAS;
-#define PG_HRX(T, MODE_, EFV, CK, TH, BN, ...)                      \
-  if (tile == T && m == MODE_ && ef == (EFV) && d->cout == BN)      \
-    return launch_hr_ef<CK, TH, BN, MODE_, (EFV), ##__VA_ARGS__>(d, a, st);
-  // tile 0: 16 -> 16 (1024^2: D conv a fwd / dgrad / tangent, G conv b fwd / dgrad)
-  PG_HRX(0, HR_PLAIN, 0, 16, 16, 16, PG_EF_NW)
-  PG_HRX(0, HR_PLAIN, PG_CONV_LRELU | PG_CONV_BIAS, 16, 16, 16, PG_EF_NW)
-  PG_HRX(0, HR_PLAIN, PG_CONV_MASK, 16, 16, 16, PG_EF_NW)
-  PG_HRX(0, HR_PLAIN, PN, 16, 16, 16, PG_EF_NW)
-  PG_HRX(0, HR_PLAIN, PN | Y, 16, 16, 16, PG_EF_NW)
-  // ... with the toRGB output in the epilogue (the generator's top conv b, alpha = 1)
-  PG_HRX(0, HR_PLAIN, PN | PG_CONV_RGBO, 16, 16, 16, PG_EF_NW)
-  PG_HRX(0, HR_PLAIN, PN | Y | PG_CONV_RGBO, 16, 16, 16, PG_EF_NW)
-  PG_HRX(0, HR_PLAIN, PG_CONV_PNBWD | Y, 16, 16, 16, PG_EF_NW)
-  // conv a forward with the sign bits of its activation; its lrelu' consumers from those bits
-  PG_HRX(0, HR_YB, PG_CONV_Y2_BITS | PG_CONV_LRELU | PG_CONV_BIAS | Y, 16, 16, 16, PG_EF_NW)
-  PG_HRX(0, HR_AB, PG_CONV_AUX_BITS | PG_CONV_MASK, 16, 16, 16, PG_EF_NW)
-  // ... with the fromRGB weight gradient in the epilogue (the final backward pass)
-  PG_HRX(0, HR_AB, PG_CONV_AUX_BITS | PG_CONV_MASK | PG_CONV_RGBW, 16, 16, 16, PG_EF_NW)
-  // ... with the fromRGB input gradient (the penalty's and the G half's passes)
-  PG_HRX(0, HR_AB, PG_CONV_AUX_BITS | PG_CONV_MASK | PG_CONV_RGBD, 16, 16, 16, PG_EF_NW)
-  // tile 1: 16 -> 32 (1024^2: D conv b fwd (sign bits) / tangent, G conv a dgrad)
-  PG_HRX(1, HR_YB, PG_CONV_Y2_BITS | PG_CONV_POOL | PG_CONV_LRELU | PG_CONV_BIAS | Y, 16, 16, 32, PG_EF_NW)
-  PG_HRX(1, HR_AB, PG_CONV_AUX_BITS | PG_CONV_POOL | PG_CONV_MASK, 16, 16, 32, PG_EF_NW)
-  PG_HRX(1, HR_PLAIN, PG_CONV_POOL, 16, 16, 32, PG_EF_NW)
-  PG_HRX(1, HR_PLAIN, PG_CONV_POOL | PG_CONV_ACCUM, 16, 16, 32, PG_EF_NW)
-  // the G conv-a input gradient at 1024^2 with the 512^2 block's PixelNorm backward after the pool
-  PG_HRX(1, HR_PLAIN, PG_CONV_POOL | PG_CONV_PNBWD | Y, 16, 16, 32, PG_EF_NW)
-  // tile 4: 32 -> 16 (1024^2: D conv b dgrad with sign bits, G conv a fwd)
-  PG_HRX(4, HR_XB, PG_CONV_X_BITS | PG_CONV_MASK | PG_CONV_UPS_IN, 32, 16, 16, PG_EF_NW)
-  PG_HRX(4, HR_XAB, PG_CONV_X_BITS | PG_CONV_AUX_BITS | PG_CONV_MASK | PG_CONV_UPS_IN, 32, 16, 16, PG_EF_NW)
-  PG_HRX(4, HR_PLAIN, PN | PG_CONV_UPS_IN, 32, 16, 16, PG_EF_NW)
-  PG_HRX(4, HR_PLAIN, PN | PG_CONV_UPS_IN | Y, 32, 16, 16, PG_EF_NW)
-  // tile 5: 32 -> 32 (512^2: D conv a, G conv b)
-  PG_HRX(5, HR_PLAIN, 0, 32, 16, 32, PG_EF_NW)
-  PG_HRX(5, HR_PLAIN, PG_CONV_LRELU | PG_CONV_BIAS, 32, 16, 32, PG_EF_NW)
-  PG_HRX(5, HR_PLAIN, PG_CONV_MASK, 32, 16, 32, PG_EF_NW)
-  PG_HRX(5, HR_PLAIN, PN, 32, 16, 32, PG_EF_NW)
-  PG_HRX(5, HR_PLAIN, PN | Y, 32, 16, 32, PG_EF_NW)
-  PG_HRX(5, HR_PLAIN, PN | PG_CONV_RGBO, 32, 16, 32, PG_EF_NW)
-  PG_HRX(5, HR_PLAIN, PN | Y | PG_CONV_RGBO, 32, 16, 32, PG_EF_NW)
-  PG_HRX(5, HR_PLAIN, PG_CONV_PNBWD | Y, 32, 16, 32, PG_EF_NW)
-  PG_HRX(5, HR_YB, PG_CONV_Y2_BITS | PG_CONV_LRELU | PG_CONV_BIAS | Y, 32, 16, 32, PG_EF_NW)
-  PG_HRX(5, HR_AB, PG_CONV_AUX_BITS | PG_CONV_MASK, 32, 16, 32, PG_EF_NW)
-  PG_HRX(5, HR_AB, PG_CONV_AUX_BITS | PG_CONV_MASK | PG_CONV_RGBW, 32, 16, 32, PG_EF_NW)
-  PG_HRX(5, HR_AB, PG_CONV_AUX_BITS | PG_CONV_MASK | PG_CONV_RGBD, 32, 16, 32, PG_EF_NW)
-  // tile 14: 32 -> 64 (512^2: D conv b fwd (sign bits) / tangent), conv_hr_t14ef
-  PG_HRX(14, HR_YB, PG_CONV_Y2_BITS | PG_CONV_POOL | PG_CONV_LRELU | PG_CONV_BIAS | Y, 32, 16, 64, PG_T14_NW)
-  PG_HRX(14, HR_AB, PG_CONV_AUX_BITS | PG_CONV_POOL | PG_CONV_MASK, 32, 16, 64, PG_T14_NW)
-  // tile 15: 64 -> 32 (512^2: G conv a fwd with PixelNorm, D conv b input gradient)
-  PG_HRX(15, HR_PLAIN, PN | PG_CONV_UPS_IN, 64, PG_T15_TH, 32)
-  PG_HRX(15, HR_PLAIN, PN | PG_CONV_UPS_IN | Y, 64, PG_T15_TH, 32)
-  PG_HRX(15, HR_XB, PG_CONV_X_BITS | PG_CONV_MASK | PG_CONV_UPS_IN, 64, PG_T15_TH, 32)
-  PG_HRX(15, HR_XAB, PG_CONV_X_BITS | PG_CONV_AUX_BITS | PG_CONV_MASK | PG_CONV_UPS_IN, 64, PG_T15_TH, 32)
-  // tile 16: 64 -> 64 (256^2: D conv a, G conv b; forward, input gradient, tangent)
-  PG_HRX(16, HR_PLAIN, 0, 64, PG_T16_TH, 64, PG_T16_NW)
-  PG_HRX(16, HR_PLAIN, PG_CONV_LRELU | PG_CONV_BIAS, 64, PG_T16_TH, 64, PG_T16_NW)
-  PG_HRX(16, HR_PLAIN, PG_CONV_MASK, 64, PG_T16_TH, 64, PG_T16_NW)
-  PG_HRX(16, HR_PLAIN, PN, 64, PG_T16_TH, 64, PG_T16_NW)
-  PG_HRX(16, HR_PLAIN, PN | Y, 64, PG_T16_TH, 64, PG_T16_NW)
-#undef PG_HRX
-  return PG_ERR_UNSUPPORTED;
+template <size_t... I>
+int launch_hr_row(size_t row, const pg_conv_desc* d, const ConvArgs& a, hipStream_t st,
+                  std::index_sequence<I...>) {
+  using Fn = int (*)(const pg_conv_desc*, const ConvArgs&, hipStream_t);
+  static constexpr Fn fn[] = {launch_conv_hr<(int)I>...};
+  return fn[row](d, a, st);
 }
 
 int conv_hr_dispatch(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
-  const int m = conv_hr_mode(d);
-  PG_CHECK_ARG(conv_hr_mode_ok(d), "conv_hr: sign-bit mode %d not instantiated for this tile", m);
-#define PG_HR(T, ...)                                                       \
-  case T:                                                                   \
-    if constexpr (T == 4 || T == 8 || T == 5) {                             \
-      if (m == HR_XB) return launch_hr_pd<__VA_ARGS__, HR_XB>(d, a, st);    \
-      if (m == HR_XAB) return launch_hr_pd<__VA_ARGS__, HR_XAB>(d, a, st);  \
-    }                                                                       \
-    if constexpr (T == 1 || T == 3) {                                       \
-      if (m == HR_YB) return launch_hr_pd<__VA_ARGS__, HR_YB>(d, a, st);    \
-      if (m == HR_AB) return launch_hr_pd<__VA_ARGS__, HR_AB>(d, a, st);    \
-    }                                                                       \
-    return launch_hr_pd<__VA_ARGS__, HR_PLAIN>(d, a, st);
-  const int tile = conv_hr_tile(d);
-  // tiles 3 (32 x 16 pixels x 64 channels, 8 waves) and 6 (16 x 16 x 64, 4 waves) with
-  // LDS-DMA double-buffered staging
-  if (tile == 6 && m == HR_PLAIN && cinp_of(d->cin) % 32 == 0) {
-    if (PG_T6_NW == 8)   // the 8-wave asm-DMA form of tile 3 on 16-row tiles (two waves per SIMD)
-      return launch_conv_hr<32, 16, 64, false, 8, HR_PLAIN, 1, true, true>(d, a, st);
-    return launch_conv_hr<32, 16, 64, false, 4, HR_PLAIN, 1, false, true>(d, a, st);
-  }
-  if (tile == 13)   // conv_hr_t13 checked the mode (plain) and the geometry; two LDS slots
-    return launch_conv_hr<32, 8, 64, false, 4, HR_PLAIN, 1, false, true>(d, a, st);
-  if (tile == 3 && cinp_of(d->cin) % 32 == 0) {
-    // the inline-asm DMA form (overlapped staging, masks after the loop): A/B 298.0 -> 305.3
-    // img/s, 5-7 % per launch
-    if (m == HR_YB) return launch_conv_hr<32, 32, 64, false, PG_T3B_NW, HR_YB, 1, true, true>(d, a, st);
-    if (m == HR_AB) return launch_conv_hr<32, 32, 64, false, PG_T3B_NW, HR_AB, 1, true, true>(d, a, st);
-    if (m == HR_PLAIN)
-      return launch_conv_hr<32, 32, 64, false, PG_T3_NW, HR_PLAIN, 1, true, true>(d, a, st);
-  }
-  if (tile == 0 || tile == 1 || tile == 4 || tile == 5 || tile == 14 || tile == 15 || tile == 16) {
-    const int rc = conv_hr_ef_dispatch(tile, m, d, a, st);
-    if (rc != PG_ERR_UNSUPPORTED) return rc;
-    // tile 14's sign-bit modes and the unpooled YB / AB launches of tiles 0, 5 exist only as
-    // the EF launches above
-    PG_CHECK_ARG(tile != 14 || m == HR_PLAIN, "conv_hr: tile 14 sign-bit launch without its EF variant");
-    PG_CHECK_ARG(tile != 15 && tile != 16, "conv_hr: tile %d launch without its EF variant (flags %d)",
-                 tile, d->flags);
-    PG_CHECK_ARG(!((tile == 0 || tile == 5) && (m == HR_YB || m == HR_AB)),
-                 "conv_hr: tile %d sign-bit launch (flags %d) without its EF variant", tile, d->flags);
-  }
-  switch (tile) {
-    PG_HR(0, 16, 16, 16, true, 4)
-    PG_HR(1, 16, 16, 32, true, 4)
-    PG_HR(2, 16, 16, 64, false, 4)
-    // wide outputs: 8 waves over a 32-row tile (two waves per SIMD at the same per-wave
-    // tile) when that still gives a workgroup per CU
-    PG_HR(3, 32, 32, 64, false, 8)
-    PG_HR(4, 32, 16, 16, true, 4)
-    PG_HR(5, 32, 16, 32, true, 4)
-    PG_HR(6, 32, 16, 64, false, 4)
-    PG_HR(7, 32, 16, 16, false, 4)
-    PG_HR(8, 32, 16, 32, false, 4)
-  }
-#undef PG_HR
-  return PG_ERR_ARG;
+  const HrRow* r = conv_hr_select(d, a.y2 != nullptr);
+  PG_CHECK_ARG(r, "conv3x3_fwd: no conv_hr variant takes flags 0x%x %s y2 for %d -> %d at %dx%d (B %d)",
+               d->flags, a.y2 ? "with" : "without", d->cin, d->cout, d->H, d->W, d->B);
+  return launch_hr_row(r - HR_ROWS, d, a, st, std::make_index_sequence<HR_NROWS>{});
 }
+

@@ -2,10 +2,12 @@
 include/pggan_hip.h declares, the ctypes table of pggan_amd/_lib.py declares each of them,
 and the host-only entry points (step plan, workspace sizes, packed sizes) answer."""
 import ctypes
+import itertools
 import os
 import re
 
 import pytest
+import torch
 
 from pggan_amd import _lib
 
@@ -51,6 +53,57 @@ def test_step_plan_on_the_host(lib):
     assert any(l.startswith("D b") and "1024x1024" in l and "conv_hr" in l for l in lines), text
     with pytest.raises(RuntimeError):
         ops.step_plan(depths, 9, 4)          # stage beyond the depth list
+
+
+def test_conv_support_query_agrees_with_the_launch(lib):
+    """pg_conv3x3_supported and pg_conv3x3_fwd read one variant table: what the query calls
+    supported the launch does not refuse as a bad argument, and what it calls unsupported the
+    launch refuses.  Launch attempts with dummy pointers, so only where no device exists (a
+    launch that passes the host checks ends in PG_ERR_HIP there).  Grid: the flag sets of the
+    compile-time-flag rows, each also with one flag added or removed."""
+    if torch.cuda.is_available():
+        pytest.skip("makes launch attempts with dummy pointers: only without a device")
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    BF, ERR_ARG = _lib.PG_BF16, -1
+    UPS, BIAS, LRELU, MASK, POOL, ACCUM, PN = (_lib.CONV_UPS_IN, _lib.CONV_BIAS, _lib.CONV_LRELU,
+                                              _lib.CONV_MASK, _lib.CONV_POOL, _lib.CONV_ACCUM,
+                                              _lib.CONV_PIXNORM)
+    Y2B, AB, XB, PNB = _lib.CONV_Y2_BITS, _lib.CONV_AUX_BITS, _lib.CONV_X_BITS, _lib.CONV_PNBWD
+    single = (UPS, BIAS, LRELU, MASK, POOL, ACCUM, PN, Y2B, AB, XB, PNB)
+    rows = (0, BIAS | LRELU, MASK, PN | BIAS | LRELU, PNB, Y2B | BIAS | LRELU, AB | MASK,
+            Y2B | POOL | BIAS | LRELU, AB | MASK | POOL, POOL, POOL | ACCUM, POOL | PNB,
+            XB | MASK | UPS, XB | AB | MASK | UPS, PN | BIAS | LRELU | UPS)
+    flag_sets = sorted({f for f in rows} | {f ^ s for f in rows for s in single})
+
+    def cinp(c):
+        return (c + 7) // 8 * 8 if c <= 16 else (c + 31) // 32 * 32
+
+    def ask(B, H, cin, cout, fl):
+        aux_cs = cout // 8 if fl & AB else cout
+        y2_cs = max(2, cout // 8) if fl & Y2B else cout
+        d = ctypes.byref(_lib.ConvDesc(B, H, H, cin, cout, cinp(cin), cout, aux_cs, y2_cs, fl, 0.2,
+                                       1.0, cinp(cin) // 8))
+        sup = lib.pg_conv3x3_supported(BF, d, 0)
+        # y2 where the flags require it (the other rows run, or fall through, without it)
+        rc = lib.pg_conv3x3_fwd(BF, d, p, p if fl & XB else None, p, p if fl & BIAS else None,
+                                p if fl & (MASK | PNB) else None, p, p if fl & (Y2B | PNB) else None,
+                                None, 0, None)
+        return sup, rc
+
+    n_sup = 0
+    for B, H, cin, cout, fl in itertools.product((1, 4), (16, 256, 1024), (16, 32, 64), (16, 32, 64),
+                                                 flag_sets):
+        sup, rc = ask(B, H, cin, cout, fl)
+        assert (rc != ERR_ARG) == bool(sup), (B, H, cin, cout, hex(fl), sup, rc, lib.pg_last_error())
+        n_sup += sup
+    assert n_sup > 1000
+    # launches the query used to promise and the launcher refused
+    assert ask(4, 256, 32, 16, XB | MASK) == (0, ERR_ARG)               # X_BITS without UPS_IN
+    assert ask(4, 256, 32, 32, BIAS | LRELU | MASK | ACCUM | Y2B | AB) == (0, ERR_ARG)   # no such row
+    assert ask(8, 1024, 128, 64, 0) == (0, ERR_ARG)                     # past the LDS-DMA input limit
+    # the 512^2 tangent's own flags run (tile 14, without y2)
+    assert ask(4, 256, 32, 64, MASK | POOL | AB)[0] == 1
 
 
 def test_merged_entry_points_reject_bad_arguments(lib):

@@ -83,6 +83,14 @@ CONV_CASES = [
     (4, 256, 64, 64, ("bias", "lrelu")),
     # the generator's input gradient through its 512^2 conv a (32 -> 64, pooled)
     (2, 256, 32, 64, ("pool",)),
+    # odd tile counts: no multiple of the compile-time-flag rows' ring depth 2, so the
+    # runtime-flag rows of tiles 0 / 5 take them
+    (1, 16, 16, 16, ("bias", "lrelu")),
+    (3, 16, 16, 16, ()),
+    (3, 16, 32, 32, ("mask",)),
+    # the remaining runtime-flag rows: tile 2 (16 -> 64) and tile 7 (two chunks -> 16)
+    (1, 16, 16, 64, ("bias", "lrelu")),
+    (1, 16, 64, 16, ("mask",)),
 ]
 
 
@@ -1036,7 +1044,8 @@ def test_conv_rgbd_epilogue(B, H, C):
         assert err <= 1e-4, (what, err)
 
 
-@pytest.mark.parametrize("B,H,C,keep", [(4, 1024, 16, True), (8, 1024, 16, False), (2, 512, 32, True)])
+@pytest.mark.parametrize("B,H,C,keep", [(4, 1024, 16, True), (8, 1024, 16, False), (2, 512, 32, True),
+                                          (1, 32, 32, False)])
 def test_conv_rgbo_epilogue(B, H, C, keep):
     """PG_CONV_RGBO (bf16): the generator's top conv b forward with PixelNorm and the toRGB output
     img = c (W y + b) in its epilogue, against the unfused pair (the same conv, then
