@@ -185,13 +185,19 @@ int pg_conv3x3_supported(int dtype, const pg_conv_desc* d, size_t ws_bytes);
 /* weight gradient, accumulates: dw[o][c][ky][kx] += scale * sum_p gz[p][o] * x[p+tap][c]
  * and, if db != NULL, the bias gradient db[o] += scale * sum_p gz[p][o] (fused: gz is read
  * once).  desc: B,H,W, cin, cout, x_cs, y_cs = gz channel stride, flags may hold
- * PG_CONV_UPS_IN.  bf16: cout and both channel strides must be multiples of 8. */
-/* ws: optional fp32 workspace (>= pg_conv3x3_wgrad_workspace_size bytes).  When the pixel
- * range is split over workgroups the partial sums go to per-split slabs of ws and a
- * second kernel adds them into dw/db; NULL or too small -> fp32 atomics per split. */
+ * PG_CONV_UPS_IN.  bf16: cout and both channel strides must be multiples of 8.  A stride left
+ * 0 (x_cs, y_cs, xb_cs) counts as the packed one: cin as packed, cout rounded up to 8, cout / 8. */
+/* ws: optional fp32 workspace (>= pg_conv3x3_wgrad_workspace_size bytes, asked with the
+ * launch's flags).  When the pixel range is split over workgroups the partial sums go to
+ * per-split slabs of ws and a second kernel adds them into dw/db in slab order; NULL or too
+ * small -> one split, slower and as deterministic. */
 /* gzbits: NULL, or with PG_CONV_GZ_BITS (bf16 only) the sign bits at full resolution (xb_cs
  * bytes per pixel) of a gz given at half resolution (channel stride y_cs). */
 size_t pg_conv3x3_wgrad_workspace_size(int dtype, const pg_conv_desc* d);
+/* 0 if pg_conv3x3_wgrad refuses this descriptor (shape, strides, flags: not every tile has a
+ * PG_CONV_GZ_BITS kernel), otherwise positive.  Which positive value (bf16: the 1-based row of
+ * the kernel table) is for diagnostics and tests, not a stable part of the ABI. */
+int pg_conv3x3_wgrad_supported(int dtype, const pg_conv_desc* d);
 int pg_conv3x3_wgrad(int dtype, const pg_conv_desc* d, const void* x, const void* gz,
                      const void* gzbits, float scale, float* dw, float* db, void* ws,
                      size_t ws_bytes, void* stream);

@@ -106,6 +106,7 @@ _SIGS = {
     "pg_conv3x3_rgbo": ([_I, ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP, _VP, _VP, _F, _VP,
                          _VP], _I),
     "pg_conv3x3_wgrad_workspace_size": ([_I, ctypes.POINTER(ConvDesc)], _SZ),
+    "pg_conv3x3_wgrad_supported": ([_I, ctypes.POINTER(ConvDesc)], _I),
     "pg_conv3x3_wgrad": ([_I, ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _F, _VP, _VP, _VP, _SZ,
                           _VP], _I),
     "pg_bias_grad": ([_I, _I, _I, _I, _VP, _F, _VP, _VP, _VP], _I),
@@ -460,17 +461,18 @@ class HipOps:
 
     def conv_supported(self, *, B, H, W, cin, cout, flags, ws_bytes=0):
         """Whether the conv kernel picked for this shape supports `flags` (fused epilogues)."""
-        if flags & CONV_GZ_BITS:       # the weight-gradient operand form (bf16 kernel only)
-            return self.dt == PG_BF16 and H % 2 == 0 and W % 2 == 0 and cout % 8 == 0
         d = ConvDesc(B, H, W, cin, cout, 0, 0, 0, 0, flags, 0.2, 1.0, 0)
+        if flags & CONV_GZ_BITS:       # the weight-gradient operand form
+            return bool(self.lib.pg_conv3x3_wgrad_supported(self.dt, ctypes.byref(d)))
         return bool(self.lib.pg_conv3x3_supported(self.dt, ctypes.byref(d), ws_bytes))
 
     def conv_workspace_bytes(self, *, B, H, W, cin, cout):
         d = ConvDesc(B, H, W, cin, cout, 0, 0, 0, 0, 0, 0.0, 1.0, 0)
         return int(self.lib.pg_conv3x3_workspace_size(ctypes.byref(d)))
 
-    def wgrad_workspace_bytes(self, *, B, H, W, cin, cout, ups=False):
-        d = ConvDesc(B, H, W, cin, cout, 0, 0, 0, 0, CONV_UPS_IN if ups else 0, 0.0, 1.0, 0)
+    def wgrad_workspace_bytes(self, *, B, H, W, cin, cout, ups=False, gz_bits=False):
+        fl = (CONV_UPS_IN if ups else 0) | (CONV_GZ_BITS if gz_bits else 0)
+        d = ConvDesc(B, H, W, cin, cout, 0, 0, 0, 0, fl, 0.0, 1.0, 0)
         return int(self.lib.pg_conv3x3_wgrad_workspace_size(self.dt, ctypes.byref(d)))
 
     def conv_wgrad(self, x, gz, dw, *, B, H, W, cin, cout, ups, scale, db=None, ws=None,

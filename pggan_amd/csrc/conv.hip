@@ -895,16 +895,12 @@ constexpr int wgb_maxhalo(int bp) { return bp == 128 ? 288 : 18 * 18; }   // pic
 __device__ __forceinline__ float bf_lo(unsigned u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bf_hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
 
-#ifndef PG_WG_PRE_ALL
-#define PG_WG_PRE_ALL 1
-#endif
 template <int MO, int NC, int WMO, int WNC, int PD, int WPE, bool GZB, int BP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE)))
 void wgrad_bf16_kernel(WgBParams p) {
-  // precomputed per-lane staging offsets + shifts for the tile origin (every tile when
-  // PG_WG_PRE_ALL; the 64-bit per-load address math of the other form put each wide-tile
-  // halo load behind its own branch, ~600 instructions of staging per 72 MFMAs)
-  constexpr bool PRE = PG_WG_PRE_ALL || MO < 4;
+  // Staging uses precomputed per-lane offsets + shifts for the tile origin, on every tile (the
+  // 64-bit per-load address math the wide tiles once used instead put each of their halo loads
+  // behind its own branch, ~600 instructions of staging per 72 MFMAs)
   constexpr int KW = 4 / (WMO * WNC);
   constexpr int BO = WMO * MO * 16, BC = WNC * NC * 16;
   constexpr int GV = BO / 8, HV = BC / 8;
@@ -990,7 +986,7 @@ void wgrad_bf16_kernel(WgBParams p) {
     // upsample's floor shift splits: (t0 + h - 1) >> 1 = t0 / 2 + ((h - 1) >> 1))
     const int pk = hpk[k] < 0 ? 0 : hpk[k];
     const int ys = p.ups ? 1 : 0;
-    if constexpr (PRE) hrel[k] = (((pk >> 24) * p.Hin + ((((pk >> 16) & 0xff) - 1) >> ys)) * p.Win +
+    hrel[k] = (((pk >> 24) * p.Hin + ((((pk >> 16) & 0xff) - 1) >> ys)) * p.Win +
                ((((pk >> 8) & 0xff) - 1) >> ys)) * p.x_cs + 8 * (pk & 0xff);
   }
   // ok masks of a loaded tile: bit k of gz vector k / halo vector k (zero fill at the
@@ -998,11 +994,10 @@ void wgrad_bf16_kernel(WgBParams p) {
   auto load_tile = [&](int t, u32x4_t (&rg)[NGZ], u32x4_t (&rh)[NH], int (&rb)[NGZ],
                        unsigned& gok, unsigned& hok) {
     // tile -> origin (wave-uniform, scalar; shifts where the tile counts are powers of 2)
-    constexpr bool sh = PRE;
-    const int tx0 = (sh && p.lg_tx >= 0 ? (t & (p.tiles_x - 1)) : t % p.tiles_x) * p.TW;
-    const int tt = sh && p.lg_tx >= 0 ? t >> p.lg_tx : t / p.tiles_x;
-    const int ty0 = (sh && p.lg_ty >= 0 ? (tt & (p.tiles_y - 1)) : tt % p.tiles_y) * p.TH;
-    const int b0 = (sh && p.lg_ty >= 0 ? tt >> p.lg_ty : tt / p.tiles_y) * p.NB;
+    const int tx0 = (p.lg_tx >= 0 ? (t & (p.tiles_x - 1)) : t % p.tiles_x) * p.TW;
+    const int tt = p.lg_tx >= 0 ? t >> p.lg_tx : t / p.tiles_x;
+    const int ty0 = (p.lg_ty >= 0 ? (tt & (p.tiles_y - 1)) : tt % p.tiles_y) * p.TH;
+    const int b0 = (p.lg_ty >= 0 ? tt >> p.lg_ty : tt / p.tiles_y) * p.NB;
     const int gs = gz_bits ? 1 : 0;
     gok = 0;
     hok = 0;
@@ -1019,22 +1014,15 @@ void wgrad_bf16_kernel(WgBParams p) {
     }
     const int ys = p.ups ? 1 : 0;
     // the tile's input origin (scalar) + the lane's precomputed offset
-    const bf16_t* xt = PRE ? p.x + c0 + (((size_t)b0 * p.Hin + (ty0 >> ys)) * p.Win + (tx0 >> ys)) * p.x_cs
-                              : p.x;
+    const bf16_t* xt = p.x + c0 + (((size_t)b0 * p.Hin + (ty0 >> ys)) * p.Win + (tx0 >> ys)) * p.x_cs;
 #pragma unroll
     for (int k = 0; k < NH; ++k) {
       const int pk = hpk[k];
       const int yy = ty0 + ((pk >> 16) & 0xff) - 1, xx = tx0 + ((pk >> 8) & 0xff) - 1;
       const bool ok = pk >= 0 && b0 + (pk >> 24) < p.B && (unsigned)yy < (unsigned)p.H &&
                       (unsigned)xx < (unsigned)p.W;
-      if constexpr (PRE) {   // precomputed offsets (A/B: -7..-13 % at 1024^2)
-        rh[k] = *reinterpret_cast<const u32x4_t*>(ok ? xt + hrel[k] : p.x);
-      } else {                  // wide tiles: registers are tighter than VALU (+2 % the other way)
-        rh[k] = *reinterpret_cast<const u32x4_t*>(
-            ok ? p.x + c0 + (((size_t)(b0 + (pk >> 24)) * p.Hin + (yy >> ys)) * p.Win + (xx >> ys)) * p.x_cs +
-                     8 * (pk & 0xff)
-               : p.x);
-      }
+      // precomputed offsets (A/B: -7..-13 % at 1024^2)
+      rh[k] = *reinterpret_cast<const u32x4_t*>(ok ? xt + hrel[k] : p.x);
       hok |= (ok ? 1u : 0u) << k;
     }
   };
@@ -1325,192 +1313,6 @@ __global__ __launch_bounds__(64) void wgrad_slab_reduce4(const float* ws, size_t
   for (int e = 0; e < 4; ++e) dst[e] += s[e] * scale;
 }
 
-struct WgbPlan {
-  int MO, NC, WMO, WNC, BP;
-  int ot, ct, splits, tiles_per_split, ntiles;
-  TileCfg tc;
-  size_t slab;
-};
-
-bool wgrad_dma_ok(const pg_conv_desc* d, const WgbPlan& pl);
-
-WgbPlan wgrad_bf16_plan(const pg_conv_desc* d) {
-  WgbPlan pl;
-  const int co = d->cout, ci = d->cin;
-  pl.MO = co <= 16 ? 1 : co <= 32 ? 2 : 4;
-  pl.NC = 1;
-  pl.WMO = 1;
-  // two 16-channel halves of a 32-channel input slice per workgroup (waves split the
-  // channels, the gz tile is staged once for both): A/B -5..-22 % at 32^2-256^2 for
-  // cin > 32; below 32^2 the single-half tile is faster (the LDS-DMA kernel, which needs
-  // WNC = 2, measured 28.6 vs 24.1 us at 16^2 512 -> 512)
-  pl.WNC = ci <= 16 ? 1 : (ci <= 32 || d->W >= 32) ? 2 : 1;
-  // ... unless the single-half tiles overflow one round of workgroups (the 513-channel
-  // minibatch-stddev conv at 4^2: 8 x 33 = 264 > 256 ran as two rounds, 29.6 us vs 15.8)
-  if (pl.WNC == 1 && ci > 16 && pg_cdiv(co, co <= 16 ? 16 : co <= 32 ? 32 : 64) * pg_cdiv(ci, 16) > 256)
-    pl.WNC = 2;
-  const int BO = pl.WMO * pl.MO * 16, BC = pl.WNC * pl.NC * 16;
-  // 128-pixel tiles (256-pixel ones measured -6..-10 % for the single-half tile at 32^2-128^2,
-  // where the two-half tile is faster still, and +50 % with two halves: spills)
-  pl.BP = WGB_BP;
-  pl.tc = pick_tile(d->H, d->W, pl.BP, 32);
-  pl.ntiles = pg_cdiv(d->B, pl.tc.NB) * (d->W / pl.tc.TW) * (d->H / pl.tc.TH);
-  pl.ot = pg_cdiv(co, BO);
-  pl.ct = pg_cdiv(ci, BC);
-  const int base = pl.ot * pl.ct;
-  // >= 256 workgroups without a split when the output tiles allow it; otherwise split
-  // the pixels up to ~1024 workgroups, keeping >= 2 tiles per split
-  // wide (MO = 4) tiles run one workgroup per CU with 4 tiles of loads in flight: one
-  // wave of workgroups; the HBM-bound narrow ones use ~4 per CU
-  // (tools/wg_target_sweep.sh: 512 for the narrow tiles, 80.9 -> 59.2 us at 512^2 32->32,
-  // 86 -> 79 at 1024^2 16->16, 108 -> 99 at 1024^2 16->32: half the slab traffic)
-  // wide: 192 rather than one workgroup per CU (256): the weight gradients run on the side
-  // stream beside the input-gradient chain, and leaving a quarter of the CUs to the main
-  // stream's launches measured +0.2-0.6 % per step in 5 of 5 interleaved rounds (128: -2.6 %;
-  // profiles/r5_dp_ab.txt section 9)
-  int target = pl.MO >= 4 ? 192 : 512;   // narrow: 384 measured slower (r5_dp_ab.txt section 10)
-  // the LDS-DMA narrow tiles (tools/wg_target_dma.sh): (2,2) at 512^2 in one round of
-  // workgroups (8 waves at 164 VGPRs: one workgroup per CU), 51.0 -> 48.8 us at 32->32;
-  // (1,1) at 1024^2 with ~4 per CU, 74.3 -> 62.7 us at 16->16
-  if (pl.MO < 4) {
-    pl.tiles_per_split = 1;
-    if (wgrad_dma_ok(d, pl)) {
-      if (pl.MO == 2 && pl.WNC == 2) target = 256;
-      else if (pl.MO == 1 && pl.WNC == 1) target = 1024;
-    }
-  }
-  int splits = base >= 256 ? 1 : pg_cdiv(target, base);
-  const int max_splits = pl.ntiles / 2 > 1 ? pl.ntiles / 2 : 1;
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  pl.tiles_per_split = pg_cdiv(pl.ntiles, splits);
-  pl.splits = pg_cdiv(pl.ntiles, pl.tiles_per_split);
-  pl.slab = (size_t)co * ci * 9 + co;
-  return pl;
-}
-
-size_t wgrad_bf16_ws_bytes(const pg_conv_desc* d) {
-  WgbPlan pl = wgrad_bf16_plan(d);
-  return pl.splits > 1 ? pl.splits * pl.slab * sizeof(float) : 0;
-}
-
-// The second launch of the WG_SLABS mode: the split partials summed into dw / db
-int wgrad_slab_finish(const pg_conv_desc* d, const WgbPlan& pl, int mode, const float* ws, float* dw,
-                      float* db, float scale, hipStream_t st) {
-  if (mode != WG_SLABS) return PG_OK;
-  if (pl.slab >= 65536 && pl.slab % 4 == 0 && ((uintptr_t)ws & 15) == 0) {
-    // wide layers (>= 256 blocks of 64 threads): vector form, one thread sums every split
-    PG_KLAUNCH(wgrad_slab_reduce4, dim3((unsigned)pg_cdiv((long long)pl.slab / 4, 64)), dim3(64), 0, st,
-                       ws, pl.slab, pl.splits, d->cout * d->cin * 9, dw, db, scale);
-    PG_LAUNCH_CHECK();
-    return PG_OK;
-  }
-  launch_slab_reduce(ws, pl.slab, pl.splits, d->cout * d->cin * 9, dw, db, scale, st);
-  PG_LAUNCH_CHECK();
-  return PG_OK;
-}
-
-// the LDS-DMA weight gradient of the wide layers (wgrad_dma.inc)
-bool wgrad_dma_ok(const pg_conv_desc* d, const WgbPlan& pl);
-int launch_wgrad_dma(const pg_conv_desc* d, const WgbPlan& pl, const void* x, const void* gz, float scale,
-                     float* dw, float* db, float* ws, size_t ws_bytes, hipStream_t st, const void* gzbits);
-
-template <int MO, int NC, int WMO, int WNC, int PD, int WPE, bool GZB = false, int BP = WGB_BP>
-int launch_wgrad_bf16(const pg_conv_desc* d, const WgbPlan& pl, const void* x, const void* gz,
-                      float scale, float* dw, float* db, float* ws, size_t ws_bytes,
-                      hipStream_t st, const void* gzbits) {
-  constexpr int BO = WMO * MO * 16, BC = WNC * NC * 16;
-  WgBParams p;
-  p.x = (const bf16_t*)x; p.gz = (const bf16_t*)gz; p.dw = dw; p.db = db;
-  p.B = d->B; p.H = d->H; p.W = d->W;
-  p.ups = (d->flags & PG_CONV_UPS_IN) ? 1 : 0;
-  p.Hin = p.ups ? d->H / 2 : d->H;
-  p.Win = p.ups ? d->W / 2 : d->W;
-  p.cin = d->cin; p.cout = d->cout; p.x_cs = d->x_cs; p.gz_cs = d->y_cs;
-  p.scale = scale;
-  p.NB = pl.tc.NB; p.TH = pl.tc.TH; p.TW = pl.tc.TW;
-  p.tiles_x = d->W / pl.tc.TW;
-  p.tiles_y = d->H / pl.tc.TH;
-  auto lg2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; };
-  p.lg_tx = lg2(p.tiles_x);
-  p.lg_ty = lg2(p.tiles_y);
-  p.ntiles = pl.ntiles;
-  p.tiles_per_split = pl.tiles_per_split;
-  p.GZS = BO + (BO > 16 ? 16 : 0);
-  p.HS = BC == 16 ? 16 : BC + 16;
-  p.hpad = pl.tc.TW >= 8 ? 64 : 0;
-  p.halo_elems = pl.tc.NB * (pl.tc.TH + 2) * (pl.tc.TW + 2);
-  p.gzb = (d->flags & PG_CONV_GZ_BITS) ? reinterpret_cast<const unsigned char*>(gzbits) : nullptr;
-  p.gzb_cs = d->xb_cs;
-  p.slope = d->slope;
-  p.xcd_remap = 1;
-  PG_CHECK_ARG(!p.gzb || (d->xb_cs * 8 >= d->cout && pl.tc.TH % 2 == 0 && pl.tc.TW % 2 == 0),
-               "wgrad_bf16: GZ_BITS needs gzbits with >= cout/8 bytes per pixel");
-  PG_CHECK_ARG(pl.BP == BP && p.halo_elems <= wgb_maxhalo(BP), "wgrad_bf16: halo %d > %d", p.halo_elems,
-               wgb_maxhalo(BP));
-  p.slab = pl.slab;
-  p.ws = nullptr;
-  // wgrad_bf16_dispatch re-plans to one split when the workspace cannot hold the slabs
-  PG_CHECK_ARG(pl.splits == 1 || (ws && ws_bytes >= pl.splits * pl.slab * sizeof(float)),
-               "wgrad: split plan without its workspace");
-  p.mode = pl.splits == 1 ? WG_DIRECT : WG_SLABS;
-  if (p.mode == WG_SLABS) p.ws = ws;
-  // + 16 B: store_tile's scratch slot behind the halo
-  int lds = (BP * p.GZS + (BP / 8) * 64 + p.halo_elems * p.HS + (p.halo_elems / 8 + 1) * p.hpad) * 2 + 16;
-  const int need = 4 * 9 * 64 * 4 * 4;   // epilogue dump of one (mo, nc) block per wave
-  if (need > lds) lds = need;
-  PG_CHECK_ARG(lds <= 160 * 1024, "wgrad_bf16: LDS %d too large", lds);
-  PG_LDS_ATTR((wgrad_bf16_kernel<MO, NC, WMO, WNC, PD, WPE, GZB, BP>), 160 * 1024);
-  PG_KLAUNCH((wgrad_bf16_kernel<MO, NC, WMO, WNC, PD, WPE, GZB, BP>), dim3(pl.ot, pl.ct, pl.splits),
-                     dim3(256), lds, st, p);
-  PG_LAUNCH_CHECK();
-  return wgrad_slab_finish(d, pl, p.mode, ws, dw, db, scale, st);
-}
-
-// GZ_BITS variants: the tiles of the discriminator's conv b weight gradient at the levels
-// that keep sign bits (1024^2: cout 32 -> MO 2; 512^2: cout 64, cin 32 -> MO 4, WNC 2)
-constexpr bool wgrad_gzb_ok(int MO, int WNC, int PD, int WPE) {
-  return (MO == 2 && WNC == 1 && PD == 2 && WPE == 2) || (MO == 4 && PD == 4 && WPE == 1) ||
-         (MO == 1 && PD == 2);
-}
-
-int wgrad_bf16_dispatch(const pg_conv_desc* d, const void* x, const void* gz, float scale,
-                        float* dw, float* db, float* ws, size_t ws_bytes, hipStream_t st,
-                        const void* gzbits = nullptr) {
-  PG_CHECK_ARG(!(d->flags & PG_CONV_GZ_BITS) || gzbits, "wgrad_bf16: GZ_BITS without gzbits");
-  PG_CHECK_ARG(d->cout % 8 == 0 && d->x_cs % 8 == 0 && d->y_cs % 8 == 0,
-               "wgrad_bf16: cout (%d) and channel strides must be multiples of 8", d->cout);
-  WgbPlan pl = wgrad_bf16_plan(d);
-  if (pl.splits > 1 && !(ws && ws_bytes >= pl.splits * pl.slab * sizeof(float))) {
-    pl.splits = 1;   // no room for the slabs: one split (WG_DIRECT), deterministic
-    pl.tiles_per_split = pl.ntiles;
-  }
-  if (wgrad_dma_ok(d, pl)) return launch_wgrad_dma(d, pl, x, gz, scale, dw, db, ws, ws_bytes, st, gzbits);
-  // (prefetch depth, waves per SIMD) from the round-1 sweep
-  const int pd = pl.MO >= 4 ? 4 : 2, wpe = pl.MO >= 4 ? 1 : (pl.MO * pl.WNC >= 2 ? 2 : 3);
-  const bool gzb = (d->flags & PG_CONV_GZ_BITS) != 0;
-#define PG_WGB(a, b, c, e, PD, WPE)                                                        \
-  if (pl.MO == a && pl.NC == b && pl.WMO == c && pl.WNC == e && pd == PD && wpe == WPE) {  \
-    if constexpr (wgrad_gzb_ok(a, e, PD, WPE)) {                                           \
-      if (gzb)                                                                             \
-        return launch_wgrad_bf16<a, b, c, e, PD, WPE, true>(d, pl, x, gz, scale, dw, db,   \
-                                                            ws, ws_bytes, st, gzbits);     \
-    }                                                                                      \
-    PG_CHECK_ARG(!gzb, "wgrad_bf16: GZ_BITS not instantiated for this tile");              \
-    return launch_wgrad_bf16<a, b, c, e, PD, WPE, false>(d, pl, x, gz, scale, dw, db, ws,  \
-                                                         ws_bytes, st, gzbits);            \
-  }
-  PG_WGB(1, 1, 1, 1, 2, 3)
-  PG_WGB(1, 1, 1, 2, 2, 2)
-  PG_WGB(2, 1, 1, 1, 2, 2)
-  PG_WGB(2, 1, 1, 2, 2, 2)
-  PG_WGB(4, 1, 1, 1, 4, 1)
-  PG_WGB(4, 1, 1, 2, 4, 1)
-#undef PG_WGB
-  PG_CHECK_ARG(false, "wgrad_bf16: no kernel for plan");
-  return PG_ERR_ARG;
-}
-
 // --------------------------------------------------------------------------
 template <typename T>
 __global__ void pack_kernel(int mode, int cout, int cin, int rows, int kin, const float* w,
@@ -1741,6 +1543,291 @@ int launch_tr(const pg_conv_desc* d, const ConvArgs& a, hipStream_t st) {
 #include "conv_lr.inc"
 #include "wgrad_dma.inc"
 
+// --------------------------------------------------------------------------
+// Host side of the bf16 weight gradient.  WG_ROWS is the one list of its kernels: a row is an
+// instantiation (nothing else is instantiated) and the workgroup count its pixel split aims
+// at; wg_admits is the rule by which a row takes a launch.  pg_conv3x3_wgrad_supported, the
+// workspace query, the step plan and the launch all ask wgrad_select, so a new kernel is a new
+// row and nothing else.
+struct WgRow {
+  bool dma;      // wgrad_dma_kernel<MO, WNC, GZB>; else wgrad_bf16_kernel<MO, 1, 1, WNC, PD, WPE, GZB, 128>
+  int MO, WNC;   // 16-channel o-blocks per wave, 16-channel input halves per workgroup
+  int PD, WPE;   // register kernel: prefetch depth, waves per SIMD (the round-1 sweep)
+  bool GZB;      // PG_CONV_GZ_BITS
+  int target;    // workgroups the pixel split aims at
+};
+
+// Keyed by (MO, WNC, GZB), which wgrad_select derives from the launch; the LDS-DMA row of a key
+// comes before its register row, which takes what the DMA row's geometry does not admit.
+// kbench, LDS-DMA against register kernel per launch: (4, 2) 0.76-0.81x at 32^2-512^2; (2, 1),
+// (1, 1), (1, 2) at 1024^2 0.82-0.85x; (2, 2) at 512^2 0.96x with its own target (1.13-1.18x
+// with 512).  Targets: the wide (MO 4) tiles run one workgroup per CU with 4 tiles of loads in
+// flight, the HBM-bound narrow ones ~4 per CU.
+//   192, wide: rather than one workgroup per CU (256).  The weight gradients run on the side
+//     stream beside the input-gradient chain; leaving a quarter of the CUs to the main stream
+//     measured +0.2-0.6 % per step in 5 of 5 interleaved rounds (128: -2.6 %;
+//     profiles/r5_dp_ab.txt section 9)
+//   512, narrow: 80.9 -> 59.2 us at 512^2 32 -> 32, 86 -> 79 at 1024^2 16 -> 16, 108 -> 99 at
+//     1024^2 16 -> 32 (half the slab traffic; a round-5 sweep whose script is no longer in the
+//     tree); 384 measured slower (r5_dp_ab.txt section 10)
+//   256, LDS-DMA (2, 2): 512^2 in one round of workgroups (8 waves at 164 VGPRs: one workgroup
+//     per CU), 51.0 -> 48.8 us at 32 -> 32 (same sweep)
+//   1024, LDS-DMA (1, 1): 1024^2 with ~4 per CU, 74.3 -> 62.7 us at 16 -> 16 (same sweep)
+// GZ_BITS rows: the tiles of the discriminator's conv b weight gradient at the levels that keep
+// sign bits (1024^2: cout 32 -> MO 2; 512^2: cout 64, cin 32 -> MO 4, WNC 2) and the register
+// tiles beside them.  There is no (2, 2) GZ_BITS kernel: 16 < cout <= 32 with cin > 16 is refused.
+constexpr WgRow WG_ROWS[] = {
+    {true, 1, 1, 0, 0, false, 1024}, {false, 1, 1, 2, 3, false, 512},
+    {true, 1, 2, 0, 0, false, 512},  {false, 1, 2, 2, 2, false, 512},
+    {true, 2, 1, 0, 0, false, 512},  {false, 2, 1, 2, 2, false, 512},
+    {true, 2, 2, 0, 0, false, 256},  {false, 2, 2, 2, 2, false, 512},
+    {false, 4, 1, 4, 1, false, 192},
+    {true, 4, 2, 0, 0, false, 192},  {false, 4, 2, 4, 1, false, 192},
+    {false, 1, 1, 2, 3, true, 512},  {false, 1, 2, 2, 2, true, 512},
+    {true, 2, 1, 0, 0, true, 512},   {false, 2, 1, 2, 2, true, 512},
+    {false, 4, 1, 4, 1, true, 192},
+    {true, 4, 2, 0, 0, true, 192},   {false, 4, 2, 4, 1, true, 192},
+};
+constexpr int WG_NROWS = sizeof(WG_ROWS) / sizeof(WG_ROWS[0]);
+
+// Whether row r runs this launch: everything its launcher would refuse on the host.  d holds
+// no zero stride (wgrad_select), tc is pick_tile's 128-pixel tile.
+bool wg_admits(const WgRow& r, const pg_conv_desc& d, const TileCfg& tc) {
+  if (!r.dma) {
+    // bits at full, gz at half resolution: whole 2 x 2 blocks per tile
+    if (r.GZB && (d.xb_cs * 8 < d.cout || tc.TH % 2 || tc.TW % 2)) return false;
+    return tc.NB * (tc.TH + 2) * (tc.TW + 2) <= wgb_maxhalo(WGB_BP);   // bounds the LDS: < 55 KiB
+  }
+  // exact channel blocks, single-image 8 x 16 tiles whose index splits by shifts
+  if (tc.TW != WGD_TW || tc.TH != WGD_TH || tc.NB != 1) return false;
+  if (d.cout % (16 * r.MO) || d.cin % (16 * r.WNC)) return false;
+  const int tx = d.W / WGD_TW, ty = d.H / WGD_TH;
+  if ((tx & (tx - 1)) || (ty & (ty - 1))) return false;
+  // one dword of bits per lane
+  if (r.GZB && (d.xb_cs % 4 || d.xb_cs * 8 < d.cout)) return false;
+  // out-of-image halo pixels / bit lanes load with offset 0x7fff0000 (OOB in the kernel), which
+  // reads zeros only while it is at or past every buffer's range (num_records)
+  const int us = d.flags & PG_CONV_UPS_IN ? 2 : 1, gs = r.GZB ? 2 : 1;
+  const size_t xin = (size_t)d.B * (d.H / us) * (d.W / us) * d.x_cs * 2;
+  const size_t gin = (size_t)d.B * (d.H / gs) * (d.W / gs) * d.y_cs * 2;
+  const size_t bits = r.GZB ? (size_t)d.B * d.H * d.W * d.xb_cs : 0;
+  return xin <= 0x7fff0000ull && gin <= 0x7fff0000ull && bits <= 0x7fff0000ull;
+}
+
+struct WgSel {
+  const WgRow* row;   // nullptr: no kernel takes the launch, `why` names the rule
+  const char* why;
+  pg_conv_desc d;     // the descriptor, the strides it leaves 0 (a query) packed
+  TileCfg tc;
+  int ot, ct, ntiles, splits, tiles_per_split;
+  size_t slab;        // fp32 elements of one split's partial: dw + db
+};
+
+bool wgrad_shape_ok(const pg_conv_desc* d) {
+  return d->B > 0 && d->H >= 4 && d->W >= 4 && d->cin > 0 && d->cout > 0;
+}
+
+// The kernel and the plan of a bf16 weight gradient: a pure function of the descriptor and of
+// the bytes of workspace the launch brings (SIZE_MAX: a query, as much as the plan wants).
+WgSel wgrad_select(const pg_conv_desc* d, size_t ws_bytes) {
+  WgSel s{};
+  s.d = *d;
+  pg_conv_desc& e = s.d;
+  if (!e.x_cs) e.x_cs = cinp_of(e.cin);
+  if (!e.y_cs) e.y_cs = (e.cout + 7) & ~7;
+  if (!e.xb_cs) e.xb_cs = e.cout / 8;
+  const bool gzb = (e.flags & PG_CONV_GZ_BITS) != 0;
+  const int co = e.cout, ci = e.cin;
+  if (!wgrad_shape_ok(d)) return s.why = "bad spatial size", s;
+  if (gzb && (e.H % 2 || e.W % 2)) return s.why = "GZ_BITS needs even H, W", s;
+  if (co % 8 || e.x_cs % 8 || e.y_cs % 8)
+    return s.why = "cout and the channel strides must be multiples of 8", s;
+  // 1. the tile from the channel counts
+  const int MO = co <= 16 ? 1 : co <= 32 ? 2 : 4;
+  // two 16-channel halves of a 32-channel input slice per workgroup (waves split the
+  // channels, the gz tile is staged once for both): A/B -5..-22 % at 32^2-256^2 for
+  // cin > 32; below 32^2 the single-half tile is faster (the LDS-DMA kernel with WNC = 2
+  // measured 28.6 vs 24.1 us at 16^2 512 -> 512)
+  int WNC = ci <= 16 ? 1 : (ci <= 32 || e.W >= 32) ? 2 : 1;
+  // ... unless the single-half tiles overflow one round of workgroups (the 513-channel
+  // minibatch-stddev conv at 4^2: 8 x 33 = 264 > 256 ran as two rounds, 29.6 us vs 15.8)
+  if (WNC == 1 && ci > 16 && pg_cdiv(co, 16 * MO) * pg_cdiv(ci, 16) > 256) WNC = 2;
+  // 128-pixel tiles (256-pixel ones measured -6..-10 % for the single-half tile at 32^2-128^2,
+  // where the two-half tile is faster still, and +50 % with two halves: spills)
+  s.tc = pick_tile(e.H, e.W, WGB_BP, 32);
+  s.ntiles = pg_cdiv(e.B, s.tc.NB) * (e.W / s.tc.TW) * (e.H / s.tc.TH);
+  s.ot = pg_cdiv(co, 16 * MO);
+  s.ct = pg_cdiv(ci, 16 * WNC);
+  s.slab = (size_t)co * ci * 9 + co;
+  // 2. the first row of that tile that admits the launch
+  for (const WgRow& r : WG_ROWS)
+    if (r.MO == MO && r.WNC == WNC && r.GZB == gzb && wg_admits(r, e, s.tc)) {
+      s.row = &r;
+      break;
+    }
+  if (!s.row) return s.why = gzb ? "no GZ_BITS kernel for this tile" : "no kernel for this tile", s;
+  // 3. the pixel split: >= 256 workgroups without one when the output tiles allow it, otherwise
+  // up to the row's target, keeping >= 2 tiles per split
+  const int base = s.ot * s.ct;
+  int splits = base >= 256 ? 1 : pg_cdiv(s.row->target, base);
+  splits = std::max(1, std::min(splits, s.ntiles / 2));
+  s.tiles_per_split = pg_cdiv(s.ntiles, splits);
+  s.splits = pg_cdiv(s.ntiles, s.tiles_per_split);
+  // no room for the slabs: one split (WG_DIRECT), deterministic
+  if (s.splits > 1 && ws_bytes / sizeof(float) / s.slab < (size_t)s.splits) {
+    s.splits = 1;
+    s.tiles_per_split = s.ntiles;
+  }
+  return s;
+}
+
+struct WgArgs {
+  const void *x, *gz, *gzbits;
+  float scale;
+  float *dw, *db, *ws;
+};
+
+// The kernel parameters of both families (GZS .. halo_elems: the register kernel's LDS rows;
+// the LDS-DMA kernel has its own, WgdGeo)
+WgBParams wgrad_params(const WgSel& s, const WgArgs& a) {
+  const pg_conv_desc& d = s.d;
+  const int BO = 16 * s.row->MO, BC = 16 * s.row->WNC;
+  WgBParams p{};
+  p.x = (const bf16_t*)a.x; p.gz = (const bf16_t*)a.gz; p.dw = a.dw; p.db = a.db;
+  p.B = d.B; p.H = d.H; p.W = d.W;
+  p.ups = (d.flags & PG_CONV_UPS_IN) ? 1 : 0;
+  p.Hin = p.ups ? d.H / 2 : d.H;
+  p.Win = p.ups ? d.W / 2 : d.W;
+  p.cin = d.cin; p.cout = d.cout; p.x_cs = d.x_cs; p.gz_cs = d.y_cs;
+  p.scale = a.scale;
+  p.NB = s.tc.NB; p.TH = s.tc.TH; p.TW = s.tc.TW;
+  p.tiles_x = d.W / s.tc.TW;
+  p.tiles_y = d.H / s.tc.TH;
+  auto lg2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return (1 << l) == v ? l : -1; };
+  p.lg_tx = lg2(p.tiles_x);
+  p.lg_ty = lg2(p.tiles_y);
+  p.ntiles = s.ntiles;
+  p.tiles_per_split = s.tiles_per_split;
+  p.GZS = BO + (BO > 16 ? 16 : 0);
+  p.HS = BC == 16 ? 16 : BC + 16;
+  p.hpad = s.tc.TW >= 8 ? 64 : 0;
+  p.halo_elems = s.tc.NB * (s.tc.TH + 2) * (s.tc.TW + 2);
+  p.gzb = s.row->GZB ? reinterpret_cast<const unsigned char*>(a.gzbits) : nullptr;
+  p.gzb_cs = d.xb_cs;
+  p.slope = d.slope;
+  p.xcd_remap = 1;
+  p.slab = s.slab;
+  p.mode = s.splits == 1 ? WG_DIRECT : WG_SLABS;
+  p.ws = p.mode == WG_SLABS ? a.ws : nullptr;
+  return p;
+}
+
+// The second launch of the WG_SLABS mode: the split partials summed into dw / db
+int wgrad_slab_finish(const WgSel& s, const WgArgs& a, hipStream_t st) {
+  if (s.splits == 1) return PG_OK;
+  const int nw = s.d.cout * s.d.cin * 9;
+  if (s.slab >= 65536 && s.slab % 4 == 0 && ((uintptr_t)a.ws & 15) == 0) {
+    // wide layers (>= 256 blocks of 64 threads): vector form, one thread sums every split
+    PG_KLAUNCH(wgrad_slab_reduce4, dim3((unsigned)pg_cdiv((long long)s.slab / 4, 64)), dim3(64), 0, st,
+               a.ws, s.slab, s.splits, nw, a.dw, a.db, a.scale);
+  } else {
+    launch_slab_reduce(a.ws, s.slab, s.splits, nw, a.dw, a.db, a.scale, st);
+  }
+  PG_LAUNCH_CHECK();
+  return PG_OK;
+}
+
+template <int MO, int NC, int WMO, int WNC, int PD, int WPE, bool GZB, int BP>
+int launch_wgrad_bf16(const WgSel& s, const WgBParams& p, hipStream_t st) {
+  // gz rows + halo (+ 16 B: store_tile's scratch slot behind the halo), at least the epilogue's
+  // dump of one (mo, nc) block per wave
+  const int lds = std::max((BP * p.GZS + (BP / 8) * 64 + p.halo_elems * p.HS + (p.halo_elems / 8 + 1) * p.hpad) * 2 + 16,
+                           4 * 9 * 64 * 4 * 4);
+  PG_LDS_ATTR((wgrad_bf16_kernel<MO, NC, WMO, WNC, PD, WPE, GZB, BP>), 160 * 1024);
+  PG_KLAUNCH((wgrad_bf16_kernel<MO, NC, WMO, WNC, PD, WPE, GZB, BP>), dim3(s.ot, s.ct, s.splits),
+             dim3(256), lds, st, p);
+  PG_LAUNCH_CHECK();
+  return PG_OK;
+}
+
+template <int MO, int WNC, bool GZB>
+int launch_wgrad_dma(const WgSel& s, const WgBParams& p, hipStream_t st) {
+  using G = WgdGeo<MO, WNC, GZB>;
+  static_assert(G::NTHR * 8 * 4 <= G::LDS && G::LDS <= 160 * 1024, "wgrad_dma: LDS");
+  PG_LDS_ATTR((wgrad_dma_kernel<MO, WNC, GZB>), G::LDS);
+  PG_KLAUNCH((wgrad_dma_kernel<MO, WNC, GZB>), dim3(s.ot, s.ct, s.splits), dim3(G::NTHR), G::LDS, st, p);
+  PG_LAUNCH_CHECK();
+  return PG_OK;
+}
+
+// Launches row I.  The PG_CHECK_ARGs assert, before the first HIP call, what wgrad_select
+// promised of the row and check the operands it cannot see.
+template <int I>
+int launch_wg_row(const WgSel& s, const WgArgs& a, size_t ws_bytes, hipStream_t st) {
+  constexpr WgRow R = WG_ROWS[I];
+  PG_CHECK_ARG(s.row == &WG_ROWS[I] && wg_admits(R, s.d, s.tc), "wgrad_bf16: row %d does not take the launch", I + 1);
+  PG_CHECK_ARG(!R.GZB || a.gzbits, "wgrad_bf16: GZ_BITS without gzbits");
+  PG_CHECK_ARG(s.splits == 1 || (a.ws && ws_bytes >= s.splits * s.slab * sizeof(float)),
+               "wgrad_bf16: split plan without its workspace");
+  const WgBParams p = wgrad_params(s, a);
+  int rc;
+  if constexpr (R.dma) rc = launch_wgrad_dma<R.MO, R.WNC, R.GZB>(s, p, st);
+  else rc = launch_wgrad_bf16<R.MO, 1, 1, R.WNC, R.PD, R.WPE, R.GZB, WGB_BP>(s, p, st);
+  return rc != PG_OK ? rc : wgrad_slab_finish(s, a, st);
+}
+
+template <size_t... I>
+int launch_wg_rows(size_t row, const WgSel& s, const WgArgs& a, size_t ws_bytes, hipStream_t st,
+                   std::index_sequence<I...>) {
+  using Fn = int (*)(const WgSel&, const WgArgs&, size_t, hipStream_t);
+  static constexpr Fn fn[] = {launch_wg_row<(int)I>...};
+  return fn[row](s, a, ws_bytes, st);
+}
+
+int wgrad_bf16_dispatch(const pg_conv_desc* d, const WgArgs& a, size_t ws_bytes, hipStream_t st) {
+  const WgSel s = wgrad_select(d, a.ws ? ws_bytes : 0);
+  PG_CHECK_ARG(s.row, "conv3x3_wgrad (bf16): %s (%d -> %d at %dx%d, B %d, flags 0x%x)", s.why, d->cin,
+               d->cout, d->H, d->W, d->B, d->flags);
+  return launch_wg_rows(s.row - WG_ROWS, s, a, ws_bytes, st, std::make_index_sequence<WG_NROWS>{});
+}
+
+// The fp32 weight gradient (wgrad3x3_kernel, also the bf16 storage type's fp32-math form)
+int launch_wgrad_f32(int dtype, const pg_conv_desc* d, const WgArgs& a, size_t ws_bytes, hipStream_t st) {
+  PG_CHECK_ARG(wgrad_shape_ok(d), "conv3x3_wgrad: bad spatial size");
+  const TileCfg tc = pick_tile(d->H, d->W, WG_BP, 32);
+  WgParams p;
+  p.x = a.x; p.gz = a.gz; p.dw = a.dw; p.db = a.db;
+  p.B = d->B; p.H = d->H; p.W = d->W;
+  p.ups = (d->flags & PG_CONV_UPS_IN) ? 1 : 0;
+  p.Hin = p.ups ? d->H / 2 : d->H;
+  p.Win = p.ups ? d->W / 2 : d->W;
+  p.cin = d->cin; p.cout = d->cout; p.x_cs = d->x_cs; p.gz_cs = d->y_cs;
+  p.scale = a.scale;
+  p.NB = tc.NB; p.TH = tc.TH; p.TW = tc.TW;
+  p.tiles_x = d->W / tc.TW;
+  p.tiles_y = d->H / tc.TH;
+  p.ntiles = pg_cdiv(d->B, tc.NB) * p.tiles_x * p.tiles_y;
+  int splits = wgrad_f32_splits(d, &p.tiles_per_split);
+  p.slab = (size_t)d->cout * d->cin * 9 + d->cout;
+  p.ws = nullptr;
+  if (splits > 1 && a.ws && ws_bytes >= splits * p.slab * sizeof(float)) {
+    p.ws = a.ws;
+  } else {   // no room for the slabs: one split (deterministic, slower)
+    splits = 1;
+    p.tiles_per_split = p.ntiles;
+  }
+  const int lds = (WG_BP * WG_RS + tc.NB * (tc.TH + 2) * (tc.TW + 2) * WG_RS) * 4;
+  const dim3 grid(pg_cdiv(d->cout, WG_BO), pg_cdiv(d->cin, WG_BC), splits);
+  const int rc = pg_dispatch_dtype(dtype, "pg_conv3x3_wgrad", [&](auto t) {
+    PG_KLAUNCH(wgrad3x3_kernel<decltype(t)>, grid, dim3(256), lds, st, p);
+    return PG_OK;
+  });
+  if (rc != PG_OK) return rc;
+  if (p.ws) launch_slab_reduce(p.ws, p.slab, splits, d->cout * d->cin * 9, a.dw, a.db, a.scale, st);
+  PG_LAUNCH_CHECK();
+  return PG_OK;
+}
+
 
 // Which fused epilogues the kernel the dispatcher picks supports.
 template <typename T>
@@ -1941,56 +2028,30 @@ int pg_conv3x3_supported(int dtype, const pg_conv_desc* d, size_t ws_bytes) {
 }
 
 size_t pg_conv3x3_wgrad_workspace_size(int dtype, const pg_conv_desc* d) {
+  if (!d || !wgrad_shape_ok(d)) return 0;
+  if (dtype != PG_BF16) return wgrad_f32_ws_bytes(d);
+  const WgSel s = wgrad_select(d, SIZE_MAX);
+  return s.row && s.splits > 1 ? s.splits * s.slab * sizeof(float) : 0;
+}
+
+int pg_conv3x3_wgrad_supported(int dtype, const pg_conv_desc* d) {
   if (!d) return 0;
-  return dtype == PG_BF16 ? wgrad_bf16_ws_bytes(d) : wgrad_f32_ws_bytes(d);
+  if (dtype == PG_BF16) {
+    const WgSel s = wgrad_select(d, SIZE_MAX);
+    return s.row ? (int)(s.row - WG_ROWS) + 1 : 0;
+  }
+  return dtype == PG_F32 && wgrad_shape_ok(d) && !(d->flags & PG_CONV_GZ_BITS);
 }
 
 int pg_conv3x3_wgrad(int dtype, const pg_conv_desc* d, const void* x, const void* gz,
                      const void* gzbits, float scale, float* dw, float* db, void* ws,
                      size_t ws_bytes, void* stream) {
   PG_CHECK_ARG(d && x && gz && dw, "conv3x3_wgrad: null pointer");
-  PG_CHECK_ARG(d->B > 0 && d->H >= 4 && d->W >= 4, "conv3x3_wgrad: bad spatial size");
   const bool gzb = (d->flags & PG_CONV_GZ_BITS) != 0;
   PG_CHECK_ARG(!gzb || (gzbits && dtype == PG_BF16), "conv3x3_wgrad: GZ_BITS needs gzbits (bf16)");
-  PG_CHECK_ARG(!gzb || (d->H % 2 == 0 && d->W % 2 == 0), "conv3x3_wgrad: GZ_BITS needs even H, W");
-  if (dtype == PG_BF16)
-    return wgrad_bf16_dispatch(d, x, gz, scale, dw, db, (float*)ws, ws_bytes, (hipStream_t)stream,
-                               gzb ? gzbits : nullptr);
-  TileCfg tc = pick_tile(d->H, d->W, WG_BP, 32);
-  WgParams p;
-  p.x = x; p.gz = gz; p.dw = dw; p.db = db;
-  p.B = d->B; p.H = d->H; p.W = d->W;
-  p.ups = (d->flags & PG_CONV_UPS_IN) ? 1 : 0;
-  p.Hin = p.ups ? d->H / 2 : d->H;
-  p.Win = p.ups ? d->W / 2 : d->W;
-  p.cin = d->cin; p.cout = d->cout; p.x_cs = d->x_cs; p.gz_cs = d->y_cs;
-  p.scale = scale;
-  p.NB = tc.NB; p.TH = tc.TH; p.TW = tc.TW;
-  p.tiles_x = d->W / tc.TW;
-  p.tiles_y = d->H / tc.TH;
-  p.ntiles = pg_cdiv(d->B, tc.NB) * p.tiles_x * p.tiles_y;
-  const int ot = pg_cdiv(d->cout, WG_BO), ct = pg_cdiv(d->cin, WG_BC);
-  int splits = wgrad_f32_splits(d, &p.tiles_per_split);
-  p.slab = (size_t)d->cout * d->cin * 9 + d->cout;
-  p.ws = nullptr;
-  if (splits > 1 && ws && ws_bytes >= splits * p.slab * sizeof(float)) {
-    p.ws = (float*)ws;
-  } else {   // no room for the slabs: one split (deterministic, slower)
-    splits = 1;
-    p.tiles_per_split = p.ntiles;
-  }
-  const int lds = (WG_BP * WG_RS + tc.NB * (tc.TH + 2) * (tc.TW + 2) * WG_RS) * 4;
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid(ot, ct, splits);
-  const int rc = pg_dispatch_dtype(dtype, __func__, [&](auto t) {
-    PG_KLAUNCH(wgrad3x3_kernel<decltype(t)>, grid, dim3(256), lds, st, p);
-    return PG_OK;
-  });
-  if (rc != PG_OK) return rc;
-  if (p.ws)
-    launch_slab_reduce(p.ws, p.slab, splits, d->cout * d->cin * 9, dw, db, scale, st);
-  PG_LAUNCH_CHECK();
-  return PG_OK;
+  const WgArgs a{x, gz, gzb ? gzbits : nullptr, scale, dw, db, (float*)ws};
+  if (dtype == PG_BF16) return wgrad_bf16_dispatch(d, a, ws_bytes, (hipStream_t)stream);
+  return launch_wgrad_f32(dtype, d, a, ws_bytes, (hipStream_t)stream);
 }
 
 int pg_bias_grad(int dtype, int npix, int C, int cs, const void* g, float scale, float* db,
@@ -2031,6 +2092,7 @@ struct PlanLayer {
   int fwd_tile, dgrad_tile;
   size_t fwd_ws, dgrad_ws, wgrad_ws;
   int wg_MO, wg_WNC, wg_splits;
+  const char* wg_family;   // " dma" / " reg": the bf16 weight gradient's kernel (WG_ROWS)
 };
 }  // namespace
 
@@ -2077,12 +2139,14 @@ int pg_step_plan_create(int dtype, int n_depths, const int* depths, int stage, i
     pg_conv_desc g = d;   // input gradient: the transposed conv, cout -> cin channels
     g.cin = cout; g.cout = (cin + 3) & ~3; g.x_cs = cinp_of(cout); g.y_cs = g.cout; g.flags = 0;
     plan_conv(dtype, &g, &L.dgrad_path, &L.dgrad_tile, &L.dgrad_ws);
-    L.wgrad_ws = dtype == PG_BF16 ? wgrad_bf16_ws_bytes(&d) : wgrad_f32_ws_bytes(&d);
+    L.wgrad_ws = pg_conv3x3_wgrad_workspace_size(dtype, &d);
+    L.wg_MO = L.wg_WNC = 0; L.wg_splits = 1; L.wg_family = "";
     if (dtype == PG_BF16) {
-      const WgbPlan w = wgrad_bf16_plan(&d);
-      L.wg_MO = w.MO; L.wg_WNC = w.WNC; L.wg_splits = w.splits;
-    } else {
-      L.wg_MO = L.wg_WNC = 0; L.wg_splits = 1;
+      const WgSel w = wgrad_select(&d, SIZE_MAX);
+      if (w.row) {
+        L.wg_MO = w.row->MO; L.wg_WNC = w.row->WNC; L.wg_splits = w.splits;
+        L.wg_family = w.row->dma ? " dma" : " reg";
+      }
     }
     p->ws_bytes = std::max({p->ws_bytes, L.fwd_ws, L.dgrad_ws, L.wgrad_ws});
   };
@@ -2123,7 +2187,7 @@ int pg_step_plan_describe(const pg_step_plan* plan, char* buf, size_t len) {
     put("  dgrad %s", path[L.dgrad_path]);
     if (L.dgrad_path == 1) put("/t%d", L.dgrad_tile);
     if (L.dgrad_ws) put("/splitK");
-    put("  wgrad MO%d WNC%d splits %d\n", L.wg_MO, L.wg_WNC, L.wg_splits);
+    put("  wgrad MO%d WNC%d splits %d%s\n", L.wg_MO, L.wg_WNC, L.wg_splits, L.wg_family);
   }
   return PG_OK;
 }

@@ -1,9 +1,10 @@
-// Included inside conv.hip's anonymous namespace, after conv_hr.inc (uses WgBParams, WgbPlan,
-// tr_read8, hr_dma16, lds_void_t, the WG_* reduction modes).
+// Included inside conv.hip's anonymous namespace, after conv_hr.inc (uses WgBParams, tr_read8,
+// hr_dma16, lds_void_t, the WG_* reduction modes).  The kernel only: which launches it takes,
+// and with which plan, is in the LDS-DMA rows of WG_ROWS (conv.hip).
 //
-// wgrad_dma_kernel: the bf16 3x3 weight gradient of the wide layers (cout a multiple of 64,
-// cin a multiple of 32, W >= 16: the 32^2-512^2 levels), dW[o][c][tap] = sum_p gz[p][o] *
-// x[p + tap][c], with the same MFMA decomposition as wgrad_bf16_kernel<4, 1, 1, 2> (a
+// wgrad_dma_kernel: the bf16 3x3 weight gradient of every layer with exact 16 MO / 16 WNC
+// channel blocks and whole 8 x 16 tiles (narrow and wide layers alike), dW[o][c][tap] = sum_p gz[p][o] * x[p + tap][c].  It began as the wide layers' kernel
+// and is described for them: the same MFMA decomposition as wgrad_bf16_kernel<4, 1, 1, 2> (a
 // workgroup owns 64 o x 32 c x 9 taps, K = pixels in 128-pixel tiles of 8 x 16, fragments by
 // ds_read_b64_tr_b16) but staged the way conv_hr's wide tiles are:
 //
@@ -24,7 +25,7 @@
 //     (52 registers), so the k-loop issues MFMAs and ds_reads only.
 //
 // Bias gradient (c-block 0 only): summed from the staged gz rows in LDS.  Split over pixels
-// (blockIdx.z) with the host plan of wgrad_bf16_plan; the reduction modes are those of
+// (blockIdx.z) as wgrad_select plans it; the reduction modes are those of
 // wgrad_bf16_kernel (WG_DIRECT / WG_SLABS + wgrad_slab_reduce*).  An in-launch combine of the
 // slabs (the last split of each output tile summing them in split order) measured slower at
 // every split count (64^2 57.0 vs 44.3 us, step 353.0 vs 356.9 img/s,
@@ -349,85 +350,4 @@ __global__ __launch_bounds__(256 * WNC) void wgrad_dma_kernel(WgBParams p) {   /
     }
   }
 #endif
-}
-
-// The shapes this kernel takes: the register kernel's plan with one of the instantiated
-// (MO, WNC) pairs, exact 64- / 32- / 16-channel blocks, no GZ_BITS.  kbench against
-// wgrad_bf16_kernel: (4, 2) 0.76-0.81x per launch at 32^2-512^2; (2, 1), (1, 1), (1, 2) at
-// 1024^2 0.82-0.85x; (2, 2) at 512^2 0.96x once its plan keeps one round of workgroups
-// (1.13-1.18x with the register kernel's 512 target; wgrad_bf16_plan picks the target).
-bool wgrad_dma_ok(const pg_conv_desc* d, const WgbPlan& pl) {
-  const bool gzb = (d->flags & PG_CONV_GZ_BITS) != 0;
-  if (gzb && (!((pl.MO == 4 && pl.WNC == 2) || (pl.MO == 2 && pl.WNC == 1)) || d->xb_cs % 4 ||
-              d->xb_cs * 8 < d->cout || d->H % 2 || d->W % 2))
-    return false;
-  if (pl.NC != 1 || pl.WMO != 1 || pl.BP != 128) return false;
-  const bool pair = (pl.MO == 4 && pl.WNC == 2) ||
-                    (pl.MO == 2 && pl.WNC == 1) || (pl.MO == 1 && pl.WNC == 1) ||
-                    (pl.MO == 1 && pl.WNC == 2) || (pl.MO == 2 && pl.WNC == 2);
-  if (!pair) return false;
-  if (pl.tc.TW != WGD_TW || pl.tc.TH != WGD_TH || pl.tc.NB != 1) return false;
-  if (d->cout % (16 * pl.MO) || d->cin % (16 * pl.WNC) || d->x_cs % 8 || d->y_cs % 8) return false;
-  const int tx = d->W / WGD_TW, ty = d->H / WGD_TH;
-  if ((tx & (tx - 1)) || (ty & (ty - 1))) return false;
-  const bool ups = (d->flags & PG_CONV_UPS_IN) != 0;
-  const size_t xin = (size_t)d->B * (ups ? d->H / 2 : d->H) * (ups ? d->W / 2 : d->W) * d->x_cs * 2;
-  const size_t gin = (size_t)d->B * (gzb ? d->H / 2 : d->H) * (gzb ? d->W / 2 : d->W) * d->y_cs * 2;
-  // out-of-image halo pixels / bit lanes load with offset 0x7fff0000 (OOB in the kernel), which
-  // reads zeros only while it is at or past every buffer's range (num_records)
-  const size_t bits = gzb ? (size_t)d->B * d->H * d->W * d->xb_cs : 0;
-  return xin <= 0x7fff0000ull && gin <= 0x7fff0000ull && bits <= 0x7fff0000ull && pl.tiles_per_split >= 1;
-}
-
-template <int MO, int WNC, bool GZB = false>
-int launch_wgrad_dma_k(const WgbPlan& pl, const WgBParams& p, hipStream_t st) {
-  using G = WgdGeo<MO, WNC, GZB>;
-  static_assert(G::NTHR * 8 * 4 <= G::LDS && G::LDS <= 160 * 1024, "wgrad_dma: LDS");
-  PG_LDS_ATTR((wgrad_dma_kernel<MO, WNC, GZB>), G::LDS);
-  PG_KLAUNCH((wgrad_dma_kernel<MO, WNC, GZB>), dim3(pl.ot, pl.ct, pl.splits), dim3(G::NTHR), G::LDS, st, p);
-  PG_LAUNCH_CHECK();
-  return PG_OK;
-}
-
-int launch_wgrad_dma(const pg_conv_desc* d, const WgbPlan& pl, const void* x, const void* gz, float scale,
-                     float* dw, float* db, float* ws, size_t ws_bytes, hipStream_t st, const void* gzbits) {
-  WgBParams p{};
-  p.x = (const bf16_t*)x; p.gz = (const bf16_t*)gz; p.dw = dw; p.db = db;
-  p.B = d->B; p.H = d->H; p.W = d->W;
-  p.ups = (d->flags & PG_CONV_UPS_IN) ? 1 : 0;
-  p.Hin = p.ups ? d->H / 2 : d->H;
-  p.Win = p.ups ? d->W / 2 : d->W;
-  p.cin = d->cin; p.cout = d->cout; p.x_cs = d->x_cs; p.gz_cs = d->y_cs;
-  p.scale = scale;
-  const bool gzb = (d->flags & PG_CONV_GZ_BITS) != 0;
-  p.gzb = gzb ? reinterpret_cast<const unsigned char*>(gzbits) : nullptr;
-  p.gzb_cs = d->xb_cs;
-  p.slope = d->slope;
-  PG_CHECK_ARG(!gzb || gzbits, "wgrad_dma: GZ_BITS without gzbits");
-  p.tiles_x = d->W / WGD_TW;
-  p.tiles_y = d->H / WGD_TH;
-  auto lg2 = [](int v) { int l = 0; while ((1 << l) < v) ++l; return l; };
-  p.lg_tx = lg2(p.tiles_x);
-  p.lg_ty = lg2(p.tiles_y);
-  p.ntiles = pl.ntiles;
-  p.tiles_per_split = pl.tiles_per_split;
-  p.xcd_remap = 1;
-  p.slab = pl.slab;
-  p.ws = nullptr;
-  // wgrad_bf16_dispatch re-plans to one split when the workspace cannot hold the slabs
-  PG_CHECK_ARG(pl.splits == 1 || (ws && ws_bytes >= pl.splits * pl.slab * sizeof(float)),
-               "wgrad: split plan without its workspace");
-  p.mode = pl.splits == 1 ? WG_DIRECT : WG_SLABS;
-  if (p.mode == WG_SLABS) p.ws = ws;
-  PG_CHECK_ARG(pl.ntiles == d->B * p.tiles_x * p.tiles_y, "wgrad_dma: tile count");
-  int rc;
-  if (gzb && pl.MO == 4) rc = launch_wgrad_dma_k<4, 2, true>(pl, p, st);
-  else if (gzb) rc = launch_wgrad_dma_k<2, 1, true>(pl, p, st);
-  else if (pl.MO == 4) rc = launch_wgrad_dma_k<4, 2>(pl, p, st);
-  else if (pl.MO == 2 && pl.WNC == 2) rc = launch_wgrad_dma_k<2, 2>(pl, p, st);
-  else if (pl.MO == 2) rc = launch_wgrad_dma_k<2, 1>(pl, p, st);
-  else if (pl.WNC == 2) rc = launch_wgrad_dma_k<1, 2>(pl, p, st);
-  else rc = launch_wgrad_dma_k<1, 1>(pl, p, st);
-  if (rc != PG_OK) return rc;
-  return wgrad_slab_finish(d, pl, p.mode, ws, dw, db, scale, st);
 }

@@ -51,6 +51,9 @@ def test_step_plan_on_the_host(lib):
     assert ws > 0 and "splitK" in text
     assert any(l.startswith("G a") and "8x8" in l and "conv_lr" in l for l in lines), text
     assert any(l.startswith("D b") and "1024x1024" in l and "conv_hr" in l for l in lines), text
+    # the weight gradient's kernel family: LDS-DMA at 1024^2, the register kernel at 4^2
+    assert any(l.startswith("D b") and "1024x1024" in l and l.endswith(" dma") for l in lines), text
+    assert any("   4x4 " in l and l.endswith(" reg") for l in lines), text
     with pytest.raises(RuntimeError):
         ops.step_plan(depths, 9, 4)          # stage beyond the depth list
 
@@ -104,6 +107,69 @@ def test_conv_support_query_agrees_with_the_launch(lib):
     assert ask(8, 1024, 128, 64, 0) == (0, ERR_ARG)                     # past the LDS-DMA input limit
     # the 512^2 tangent's own flags run (tile 14, without y2)
     assert ask(4, 256, 32, 64, MASK | POOL | AB)[0] == 1
+
+
+# cin -> cout of test_gpu_ops.test_conv3x3_wgrad_gz_bits (B 2, H 16): one per GZ_BITS row
+GZ_BITS_SHAPES = [(16, 32), (32, 64), (16, 16), (32, 16), (16, 24), (16, 64), (32, 48)]
+WG_NROWS, WG_NROWS_BITS = 18, 7
+
+
+def test_wgrad_support_query_agrees_with_the_launch(lib):
+    """pg_conv3x3_wgrad_supported, pg_conv3x3_wgrad_workspace_size and pg_conv3x3_wgrad read one
+    variant table (WG_ROWS): (a) the launch refuses as a bad argument exactly what the query
+    calls unsupported; (b) the workspace the engine asks for without GZ_BITS holds the plan of
+    the same launch with it.  Launch attempts with dummy pointers, so only without a device."""
+    if torch.cuda.is_available():
+        pytest.skip("makes launch attempts with dummy pointers: only without a device")
+    from test_gpu_ops import WGRAD_CASES
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    BF, F32, ERR_ARG = _lib.PG_BF16, _lib.PG_F32, -1
+    GZB, UPS = _lib.CONV_GZ_BITS, _lib.CONV_UPS_IN
+
+    def cinp(c):
+        return (c + 7) // 8 * 8 if c <= 16 else (c + 31) // 32 * 32
+
+    def ask(B, H, cin, cout, fl, dtype=BF):
+        mk = lambda f: ctypes.byref(_lib.ConvDesc(B, H, H, cin, cout, cinp(cin), (cout + 7) // 8 * 8,
+                                                  0, 0, f, 0.2, 1.0, (cout + 7) // 8))
+        sup = lib.pg_conv3x3_wgrad_supported(dtype, mk(fl))
+        need = lib.pg_conv3x3_wgrad_workspace_size(dtype, mk(fl))
+        plain = lib.pg_conv3x3_wgrad_workspace_size(dtype, mk(fl & ~GZB))
+        ws = ctypes.cast((ctypes.c_float * 1)(), ctypes.c_void_p)     # never written: no device
+        rc = lib.pg_conv3x3_wgrad(dtype, mk(fl), p, p, p if fl & GZB else None, 1.0, p, p, ws, need,
+                                  None)
+        return sup, rc, need, plain
+
+    n_bits = 0
+    for B, H, cin, cout, gzb, ups in itertools.product(
+            (1, 4, 8), (4, 8, 16, 64, 512, 1024), (8, 16, 24, 32, 64, 128, 513),
+            (8, 16, 24, 32, 48, 64, 128, 512), (0, GZB), (0, UPS)):
+        if H >= 512 and max(cin, cout) > 64:
+            continue
+        sup, rc, need, plain = ask(B, H, cin, cout, gzb | ups)
+        where = (B, H, cin, cout, hex(gzb | ups), sup, rc, lib.pg_last_error())
+        assert (rc != ERR_ARG) == bool(sup), where                      # (a)
+        assert 0 <= sup <= WG_NROWS, where
+        if sup and gzb:
+            assert plain >= need, where + (plain, need)                 # (b)
+            n_bits += 1
+    assert n_bits > 300
+    # the tile without a GZ_BITS kernel: refused by both, taken without the flag
+    for H in (16, 1024):
+        assert ask(4, H, 32, 32, GZB)[:2] == (0, ERR_ARG)
+        sup, rc = ask(4, H, 32, 32, 0)[:2]
+        assert sup and rc != ERR_ARG
+    # fp32: no GZ_BITS, everything else
+    assert ask(4, 16, 32, 32, GZB, F32)[:2] == (0, ERR_ARG)
+    sup, rc = ask(4, 16, 32, 32, UPS, F32)[:2]
+    assert sup == 1 and rc != ERR_ARG
+    # every row is reached by a GPU op test
+    bits = [ask(2, 16, ci, co, GZB)[0] for ci, co in GZ_BITS_SHAPES]
+    assert len(set(bits)) == WG_NROWS_BITS and all(bits), bits
+    plain = {ask(B, H, ci, co, UPS if ups else 0)[0] for B, H, ci, co, ups in WGRAD_CASES}
+    assert 0 not in plain
+    assert len(plain) == WG_NROWS - WG_NROWS_BITS and not plain & set(bits), sorted(plain)
 
 
 def test_merged_entry_points_reject_bad_arguments(lib):

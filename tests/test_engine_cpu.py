@@ -86,6 +86,28 @@ def test_engine_schedule_separate_generator_forwards(name):
     run_and_check(meta, z, eng, fpG, fpD, tol=1e-3)
 
 
+def test_engine_falls_back_where_the_weight_gradient_has_no_gz_bits_kernel():
+    """A level whose conv-b weight gradient has no GZ_BITS kernel (ops.conv_supported says so:
+    e.g. two equal neighbouring depths of 32) does not plan "bits", and the step still matches
+    the reference; the levels below keep their sign-bit schedule."""
+    from cpu_ops import CONV_GZ_BITS
+
+    class NoTopGzBits(CpuOps):
+        def conv_supported(self, *, H, flags, **kw):
+            if flags & CONV_GZ_BITS and H == top:
+                return False
+            return super().conv_supported(H=H, flags=flags, **kw)
+
+    torch.set_num_threads(4)
+    meta, z = load("tiny_s3_b4_a1")
+    s = meta["s"]
+    top = 4 * 2 ** s
+    eng, fpG, fpD = build(meta, NoTopGzBits())
+    assert eng._dmode(s - 1) in ("ubits", "act")
+    assert eng._dmode(s - 2) == "bits"
+    run_and_check(meta, z, eng, fpG, fpD, tol=1e-3)
+
+
 def test_engine_options_env(monkeypatch):
     """PG_ENGINE (A/B runs) overrides the schedule defaults; unknown names raise."""
     monkeypatch.setenv("PG_ENGINE", "merge_g=0,dbits_min_res=64")

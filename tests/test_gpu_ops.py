@@ -159,7 +159,9 @@ WGRAD_CASES = [(2, 8, 32, 48, False), (2, 16, 16, 16, True), (4, 4, 513, 512, Fa
                (4, 128, 16, 32, False), (4, 32, 512, 512, False), (2, 64, 32, 16, True),
                (4, 64, 64, 128, False),
                # the 16^2 wide layer (the register-staged kernel) and the LDS-DMA kernel with ups
-               (4, 16, 512, 512, False), (2, 64, 256, 128, True)]
+               (4, 16, 512, 512, False), (2, 64, 256, 128, True),
+               # the narrow register kernels (1, 2), (2, 1), (2, 2): 8^2, below the LDS-DMA tile
+               (2, 8, 32, 16, False), (2, 8, 16, 24, False), (2, 8, 32, 32, False)]
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -189,6 +191,46 @@ def test_conv3x3_wgrad(case, dtype, use_ws):
     tol = 2e-5 if dtype == torch.float32 else 1e-4
     cmp(outs[0][0], outs[1][0], tol, "wgrad")
     cmp(outs[0][1], outs[1][1], tol, "wgrad bias")
+
+
+@pytest.mark.parametrize("use_ws", [True, False])
+@pytest.mark.parametrize("cin,cout", [(16, 32), (32, 64),      # the two LDS-DMA GZ_BITS kernels
+                                      (16, 16), (32, 16), (16, 24), (16, 64), (32, 48)])   # register
+def test_conv3x3_wgrad_gz_bits(cin, cout, use_ws):
+    """The weight gradient from the pooled-resolution gradient g (8^2) and sign bits (16^2, random
+    bytes): one shape per GZ_BITS kernel (test_abi checks that they select seven different rows),
+    with and without a workspace.  Tolerance: test_sign_bit_conv_paths' for dw / db."""
+    from cpu_ops import CONV_GZ_BITS
+    B, H, dt = 2, 16, torch.bfloat16
+    hip, cpu = ops_pair(dt)
+    assert hip.conv_supported(B=B, H=H, W=H, cin=cin, cout=cout, flags=CONV_GZ_BITS)
+    x = q(rnd(B, H, H, cinp(cin), seed=13), dt)
+    g = q(rnd(B, H // 2, H // 2, cout, seed=14), dt)
+    bits = torch.randint(0, 256, (B, H, H, cout // 8), dtype=torch.uint8,
+                         generator=torch.Generator().manual_seed(15))
+    outs = []
+    for ops, dev in ((hip, "cuda"), (cpu, "cpu")):
+        d_ = dt if dev == "cuda" else torch.float32
+        dw = torch.full((cout, cin, 3, 3), 0.5, device=dev)
+        db = torch.full((cout,), 0.25, device=dev)
+        ws = None
+        if use_ws and dev == "cuda":
+            nb = ops.wgrad_workspace_bytes(B=B, H=H, W=H, cin=cin, cout=cout, gz_bits=True)
+            ws = torch.full((max(nb // 4, 1),), float("nan"), device=dev)
+        ops.conv_wgrad(x.to(dev).to(d_), g.to(dev).to(d_), dw, B=B, H=H, W=H, cin=cin, cout=cout,
+                       ups=False, scale=0.3, db=db, ws=ws, gzbits=bits.to(dev))
+        outs.append((dw, db))
+    cmp(outs[0][0], outs[1][0], 2e-2, f"gz_bits wgrad {cin}->{cout}")
+    cmp(outs[0][1], outs[1][1], 2e-2, f"gz_bits wgrad bias {cin}->{cout}")
+
+
+def test_wgrad_gz_bits_query_refuses_the_tile_without_a_kernel():
+    """16 < cout <= 32 with cin > 16 plans the (2, 2) tile, which has no GZ_BITS kernel: the
+    query the engine plans its sign-bit levels with says so (it falls back to "ubits" / "act")."""
+    from cpu_ops import CONV_GZ_BITS
+    hip = lib().HipOps(torch.bfloat16)
+    assert not hip.conv_supported(B=4, H=512, W=512, cin=32, cout=32, flags=CONV_GZ_BITS)
+    assert hip.conv_supported(B=4, H=512, W=512, cin=32, cout=64, flags=CONV_GZ_BITS)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
