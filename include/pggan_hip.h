@@ -486,6 +486,36 @@ int pg_msssim_scale(int P, int S, int T, const float* taps, const float* a, cons
  * evaluated in double. */
 int pg_msssim_combine(int P, const float* sums, const long long* counts, float* out, void* stream);
 
+/* ---- nearest training images: exact squared L2 between 8-bit images in integers (the PGGAN
+ * paper's nearest-neighbour figure; DESIGN.md "Validation: nearest training images").
+ * Descriptor of an S x S image at the comparison resolution Rc (powers of two, 8 <= Rc <= 128,
+ * Rc <= S), f = S / Rc: the 8-bit pixels box-pooled in integers, (sum of the f x f block +
+ * f^2 / 2) / f^2 rounded down, minus 128: int8 [Rc][Rc][3] in (y, x, c) order, D = 3 Rc^2 bytes
+ * per row.  desc [B][D], sq[b] = sum of the squares of row b.  _f32 takes NCHW fp32
+ * [B][3][S][S] in [-1, 1], read as 8-bit like pg_swd_pyr_down; _u8 takes NHWC uint8
+ * [B][S][S][3].  x and desc 16-byte aligned; every source byte is read once.  B <= 65535. */
+int pg_nn_descriptors_f32(int B, int S, int Rc, const float* x, int8_t* desc, int* sq,
+                          void* stream);
+int pg_nn_descriptors_u8(int B, int S, int Rc, const uint8_t* x, int8_t* desc, int* sq,
+                         void* stream);
+/* Merges one database chunk into the running best lists of Q queries: afterwards best_d2[i] /
+ * best_idx[i] ([Q][k] int64, 1 <= k <= 16) hold the k smallest pairs (d^2, index), in
+ * lexicographic order (a tie goes to the lower index), among the pairs they held and
+ * (sq_q[i] + sq_x[j] - 2 q[i] . db[j], first_index + j), j < N.  The caller starts the lists at
+ * (INT64_MAX, -1), which is what slots beyond the rows seen so far keep; indices must differ
+ * between the chunks of one search, and then the result does not depend on how the database
+ * was split.  q [Q][D], db [N][D] int8 rows (16-byte aligned), qsq / dbsq their int32 sums of
+ * squares; D a multiple of 64, at most 49152 (so d^2 < 2^32 and the dot product fits int32);
+ * first_index + N < 2^31.  The dot products are v_mfma_i32_16x16x64_i8; a workgroup takes
+ * pg_nn_row_block() database rows and writes its k best per query to ws, a second launch merges
+ * those with the running lists: no atomics, bitwise repeatable.  ws: pg_nn_workspace_bytes(Q, N,
+ * k) of device memory, 8-byte aligned. */
+int pg_nn_row_block(void);
+size_t pg_nn_workspace_bytes(int Q, int N, int k);
+int pg_nn_search(int Q, int N, int D, int k, const int8_t* q, const int* qsq, const int8_t* db,
+                 const int* dbsq, long long first_index, long long* best_d2, long long* best_idx,
+                 void* ws, size_t ws_bytes, void* stream);
+
 /* ---- stream ordering between the engine's streams (weight gradients on a side stream).
  * torch's cross-stream events record with a system-scope release: every record writes back and
  * invalidates the L2 of all XCDs and the next kernel on that stream starts ~6.5 us late.  The

@@ -162,6 +162,12 @@ _SIGS = {
     "pg_msssim_workspace_bytes": ([_I, _I, _I], _SZ),
     "pg_msssim_scale": ([_I, _I, _I, _VP, _VP, _VP, _SZ, _I, _VP, _VP, _VP, _VP, _SZ, _VP], _I),
     "pg_msssim_combine": ([_I, _VP, _VP, _VP, _VP], _I),
+    "pg_nn_descriptors_f32": ([_I, _I, _I, _VP, _VP, _VP, _VP], _I),
+    "pg_nn_descriptors_u8": ([_I, _I, _I, _VP, _VP, _VP, _VP], _I),
+    "pg_nn_row_block": ([], _I),
+    "pg_nn_workspace_bytes": ([_I, _I, _I], _SZ),
+    "pg_nn_search": ([_I, _I, _I, _I, _VP, _VP, _VP, _VP, ctypes.c_longlong, _VP, _VP, _VP, _SZ,
+                      _VP], _I),
     "pg_step_plan_create": ([_I, _I, ctypes.POINTER(ctypes.c_int), _I, _I,
                              ctypes.POINTER(ctypes.c_void_p)], _I),
     "pg_step_plan_workspace_size": ([_VP], _SZ),
@@ -876,6 +882,67 @@ class HipOps:
         cn = (ctypes.c_longlong * 5)(*[int(v) for v in counts])
         self._chk(self.lib.pg_msssim_combine(P, _p(sums), cn, _p(out), self._s()),
                   "msssim_combine")
+
+    # -- nearest training images (pggan_amd/metrics.py, csrc/nn.hip) ----
+    def _cuda_named(self, what, *ts):
+        for t in ts:
+            if t is not None and not t.is_cuda:
+                raise RuntimeError(f"pggan_amd: {what} called with a CPU tensor (no CPU fallback)")
+
+    @property
+    def nn_row_block(self):
+        """Database rows per workgroup of nn_search (pg_nn_row_block)."""
+        return int(self.lib.pg_nn_row_block())
+
+    def nn_descriptors(self, images, Rc, desc, sq):
+        """desc int8 [B, 3 Rc^2], sq int32 [B]: the pooled 8-bit rows of images and their sums
+        of squares.  images: fp32 NCHW [B,3,S,S] in [-1, 1] (pg_nn_descriptors_f32) or uint8
+        NHWC [B,S,S,3] (pg_nn_descriptors_u8)."""
+        self._cuda_named("nn_descriptors", images, desc, sq)
+        if images.dim() != 4 or not images.is_contiguous():
+            raise RuntimeError("pggan_amd: nn_descriptors takes a contiguous batch of images")
+        B = images.shape[0]
+        if images.dtype == torch.float32 and images.shape[1] == 3 and \
+                images.shape[2] == images.shape[3]:
+            fn, S = self.lib.pg_nn_descriptors_f32, images.shape[2]
+        elif images.dtype == torch.uint8 and images.shape[3] == 3 and \
+                images.shape[1] == images.shape[2]:
+            fn, S = self.lib.pg_nn_descriptors_u8, images.shape[1]
+        else:
+            raise RuntimeError("pggan_amd: nn_descriptors takes fp32 [B,3,S,S] or uint8 [B,S,S,3], "
+                               f"got {images.dtype} {tuple(images.shape)}")
+        D = 3 * int(Rc) * int(Rc)
+        if desc.dtype != torch.int8 or sq.dtype != torch.int32 or not desc.is_contiguous() or \
+                not sq.is_contiguous() or tuple(desc.shape) != (B, D) or sq.numel() != B:
+            raise RuntimeError(f"pggan_amd: nn_descriptors writes int8 [{B}, {D}] rows and int32 "
+                               f"[{B}] sums")
+        self._chk(fn(B, S, int(Rc), _p(images), _p(desc), _p(sq), self._s()), "nn_descriptors")
+
+    def nn_search(self, q, qsq, db, dbsq, first_index, best_d2, best_idx, ws=None):
+        """Merge the k nearest rows of the chunk db int8 [N,D] (dbsq int32 [N], global indices
+        first_index ..) into the running lists best_d2 / best_idx int64 [Q,k] of the queries q
+        int8 [Q,D] (qsq int32 [Q]) (pg_nn_search).  ws: a uint8 workspace to use if it is large
+        enough (default: one kept by the op set)."""
+        self._cuda_named("nn_search", q, qsq, db, dbsq, best_d2, best_idx, ws)
+        for t, dt in ((q, torch.int8), (db, torch.int8), (qsq, torch.int32), (dbsq, torch.int32),
+                      (best_d2, torch.int64), (best_idx, torch.int64)):
+            if t.dtype != dt or not t.is_contiguous():
+                raise RuntimeError("pggan_amd: nn_search takes contiguous int8 rows, int32 sums "
+                                   "of squares and int64 best lists")
+        if q.dim() != 2 or db.dim() != 2 or best_d2.dim() != 2 or q.shape[1] != db.shape[1] or \
+                qsq.numel() != q.shape[0] or dbsq.numel() != db.shape[0] or \
+                best_d2.shape[0] != q.shape[0] or best_idx.shape != best_d2.shape:
+            raise RuntimeError("pggan_amd: nn_search: q [Q,D], qsq [Q], db [N,D], dbsq [N], "
+                               "best_d2 / best_idx [Q,k]")
+        (Q, D), N, k = q.shape, db.shape[0], best_d2.shape[1]
+        need = int(self.lib.pg_nn_workspace_bytes(Q, N, k))
+        if ws is None:
+            ws = getattr(self, "_nnws", None)
+            if ws is None or ws.numel() < need or ws.device != q.device:
+                ws = self._nnws = torch.empty(max(need, 8), dtype=torch.uint8, device=q.device)
+        self._chk(self.lib.pg_nn_search(Q, N, D, k, _p(q), _p(qsq), _p(db), _p(dbsq),
+                                        int(first_index), _p(best_d2), _p(best_idx), _p(ws),
+                                        ws.numel(), self._s()), "nn_search")
 
     def cast(self, x, y):
         self._cuda(x, y)

@@ -358,15 +358,44 @@ class BatchLoader:
                 src[torch.tensor(host_rows, device=self.dev)] = dev_miss
             if self.cache is not None:
                 self.cache.insert([idx[k] for k in miss], [src[k] for k in miss])
-        hit = [k for k in range(B) if k not in miss]
+        self._gather_cached([k for k in range(B) if k not in miss], idx, src)
+        if prefetch is not None:
+            self._submit(prefetch)
+        return self._augment(src)
+
+    def _gather_cached(self, hit, idx, src):
+        """Rows `hit` of the batch `src` from the stage's cache."""
         if hit:
             rows = torch.tensor([int(self.cache.slot[idx[k]]) for k in hit], device=self.dev)
-            if len(hit) == B:
+            if len(hit) == src.shape[0]:
                 torch.index_select(self.cache.buf, 0, rows, out=src)
             else:
                 src[torch.tensor(hit, device=self.dev)] = self.cache.buf.index_select(0, rows)
-        if prefetch is not None:
-            self._submit(prefetch)
+
+    def raw_u8(self, idx):
+        """The un-augmented images of `idx`, uint8 [B, S, S, 3] on the device: byte for byte
+        what next() augments, from wherever it is already (the stage's cache, the source cache
+        through resize_u8), else decoded now.  A read-only side door (nearest-neighbour search
+        over the training set): draws nothing from `gen`, counts as no call, fills neither
+        cache and leaves the pending prefetches alone."""
+        idx = [int(i) for i in idx]
+        B, S = len(idx), self.ds.size
+        src = torch.empty(B, S, S, 3, dtype=torch.uint8, device=self.dev)
+        hit = [k for k in range(B) if self._cached(idx[k])]
+        gpu_rows = [k for k in range(B) if k not in hit and self.src_cache is not None and
+                    self.src_cache.filled(self.ds.paths[idx[k]])]
+        host_rows = [k for k in range(B) if k not in hit and k not in gpu_rows]
+        if gpu_rows:
+            self._resize_from_source(gpu_rows, idx, src)
+        if host_rows:
+            arrs = list(self.pool.map(self.ds.load, [idx[k] for k in host_rows]))
+            src[torch.tensor(host_rows, device=self.dev)] = self._upload(np.stack(arrs))
+        self._gather_cached(hit, idx, src)
+        return src
+
+    def _augment(self, src):
+        """Flip + jitter + normalize of a uint8 batch, parameters from `gen`."""
+        B, S = src.shape[0], src.shape[1]
         params = torch.from_numpy(draw_params(B, self.gen)).to(self.dev, non_blocking=True)
         out = torch.empty(B, 3, S, S, dtype=torch.float32, device=self.dev)
         self._ws = self.ops.augment_u8(src, params, out, ws=self._ws)

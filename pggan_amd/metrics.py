@@ -15,6 +15,9 @@ calls torch.sort for the sort.
 
 And the paper's second figure, the multi-scale structural similarity between pairs of images of
 one set (MultiScaleSSIM below; csrc/msssim.hip through the op set's msssim_* methods).
+
+And its nearest-neighbour figure: the training images closest to given images in pixel space
+(NearestNeighbours below; csrc/nn.hip through the op set's nn_* methods).
 """
 from __future__ import annotations
 
@@ -241,3 +244,105 @@ class MultiScaleSSIM:
         """The mean over the pairs, taken in float64."""
         self._check_full("result")
         return float(self.values().double().mean().item())
+
+
+# ------------------------------------------------------------------------ nearest neighbours
+NN_MAX_K = 16
+NN_NONE = (1 << 63) - 1      # d^2 of a slot beyond the database size; its index is -1
+
+
+class NearestNeighbours:
+    """The k training images nearest to each query image: exact squared L2 between the 8-bit
+    images box-pooled to `compare` x `compare`, in integers (DESIGN.md "Validation: nearest
+    training images"; csrc/nn.hip through the op set's nn_* methods).  Ties go to the lower
+    index; how the database is split into feeds does not matter.
+
+        m = NearestNeighbours(ops, 256, 3)
+        m.set_queries(fakes)                        # fp32 [Q, 3, 256, 256] in [-1, 1]
+        for first, batch in database: m.feed(batch, first)     # or uint8 [B, 256, 256, 3]
+        idx, d2 = m.result()                        # int64 [Q, k]; (-1, INT64_MAX) past the end
+
+    Memory: the queries' rows, Q x 3 compare^2 bytes; a feed's rows live for the call."""
+
+    def __init__(self, ops, resolution, k, compare=64):
+        R, Rc, k = int(resolution), int(compare), int(k)
+        if R < 8 or R & (R - 1):
+            raise ValueError(f"NearestNeighbours: resolution must be a power of two >= 8, got {R}")
+        if Rc < 8 or Rc > 128 or Rc & (Rc - 1) or Rc > R:
+            raise ValueError(f"NearestNeighbours: compare must be a power of two in [8, "
+                             f"min(128, resolution = {R})], got {Rc}")
+        if k < 1 or k > NN_MAX_K:
+            raise ValueError(f"NearestNeighbours: k must be in [1, {NN_MAX_K}], got {k}")
+        self.ops, self.R, self.Rc, self.k, self.D = ops, R, Rc, k, 3 * Rc * Rc
+        self.q = self.qsq = self.best_d2 = self.best_idx = None
+
+    def descriptors(self, images):
+        """(int8 [B, D] rows, int32 [B] sums of squares) of fp32 NCHW or uint8 NHWC images."""
+        R = self.R
+        ok = images.dim() == 4 and (
+            (images.dtype == torch.uint8 and tuple(images.shape[1:]) == (R, R, 3)) or
+            (images.dtype != torch.uint8 and tuple(images.shape[1:]) == (3, R, R)))
+        if not ok:
+            raise ValueError(f"NearestNeighbours: expected fp32 [B, 3, {R}, {R}] or uint8 "
+                             f"[B, {R}, {R}, 3], got {images.dtype} {tuple(images.shape)}")
+        x = images.detach()
+        x = (x if x.dtype == torch.uint8 else x.to(torch.float32)).contiguous()
+        B = x.shape[0]
+        desc = torch.empty(B, self.D, dtype=torch.int8, device=x.device)
+        sq = torch.empty(B, dtype=torch.int32, device=x.device)
+        if B:
+            self.ops.nn_descriptors(x, self.Rc, desc, sq)
+        return desc, sq
+
+    def set_queries(self, images):
+        """The query images; forgets what was fed."""
+        if images.dim() != 4 or images.shape[0] < 1:
+            raise ValueError("NearestNeighbours.set_queries: at least one image")
+        self.set_query_descriptors(*self.descriptors(images))
+
+    def set_query_descriptors(self, desc, sq):
+        """The queries as prebuilt rows (descriptors()); forgets what was fed."""
+        if desc.dim() != 2 or desc.shape[0] < 1 or desc.shape[1] != self.D or \
+                desc.dtype != torch.int8 or sq.dtype != torch.int32 or \
+                tuple(sq.shape) != (desc.shape[0],):
+            raise ValueError(f"NearestNeighbours.set_query_descriptors: expected int8 [Q, "
+                             f"{self.D}] rows and int32 [Q] sums")
+        self.q, self.qsq = desc.contiguous(), sq.contiguous()
+        Q, dev = self.q.shape[0], self.q.device
+        self.best_d2 = torch.full((Q, self.k), NN_NONE, dtype=torch.int64, device=dev)
+        self.best_idx = torch.full((Q, self.k), -1, dtype=torch.int64, device=dev)
+
+    def feed(self, images, first_index):
+        """Database images with the indices first_index, first_index + 1, .."""
+        desc, sq = self.descriptors(images)
+        self.feed_descriptors(desc, sq, first_index)
+
+    def feed_descriptors(self, desc, sq, first_index):
+        """A prebuilt block of database rows (descriptors())."""
+        if self.q is None:
+            raise RuntimeError("NearestNeighbours.feed: set_queries first")
+        if desc.dim() != 2 or desc.shape[1] != self.D or desc.dtype != torch.int8 or \
+                sq.dtype != torch.int32 or tuple(sq.shape) != (desc.shape[0],):
+            raise ValueError(f"NearestNeighbours.feed_descriptors: expected int8 [N, {self.D}] "
+                             f"rows and int32 [N] sums, got {desc.dtype} {tuple(desc.shape)} and "
+                             f"{sq.dtype} {tuple(sq.shape)}")
+        if int(first_index) < 0:
+            raise ValueError("NearestNeighbours.feed_descriptors: first_index must be >= 0")
+        if desc.shape[0] == 0:
+            return
+        self.ops.nn_search(self.q, self.qsq, desc.contiguous(), sq.contiguous(), int(first_index),
+                           self.best_d2, self.best_idx)
+
+    def result(self):
+        """(idx, d2), int64 [Q, k], nearest first."""
+        if self.q is None:
+            raise RuntimeError("NearestNeighbours.result: set_queries first")
+        return self.best_idx, self.best_d2
+
+    def rms(self):
+        """sqrt(d2 / D), float64 [Q, k] on the CPU: the RMS pixel difference on the 0..255 scale
+        (inf in the slots beyond the database size).  Taken on the host, where the square root
+        is correctly rounded: the figure is a function of d2 alone, whatever ran the search."""
+        idx, d2 = (t.cpu() for t in self.result())
+        r = (d2.double() / self.D).sqrt()
+        return torch.where(idx < 0, torch.full_like(r, float("inf")), r)

@@ -19,7 +19,8 @@ Differences (deliberate):
     launch, sampled by `sample(z)`, saved beside the reference's files as `G_ema_*.pt`.
   * config `use_validation` fills in the reference's empty validation(): the paper's sliced
     Wasserstein distance on the held-out 30 % of the images (pggan_amd.metrics); config
-    `msssim_pairs` (blank: off) adds the paper's MS-SSIM between pairs of generated images.
+    `msssim_pairs` (blank: off) adds the paper's MS-SSIM between pairs of generated images,
+    `nn_queries` (blank: off) the distance to the nearest training images.
 """
 from __future__ import annotations
 
@@ -293,6 +294,10 @@ class ProgressiveGAN:
         idx = self._order[self._pos:self._pos + B]
         self._pos += B
         nxt = self._pos if self._pos + B <= len(self._order) else 0
+        return self._stage_loader().next(idx, prefetch=self._order[nxt:nxt + B])
+
+    def _stage_loader(self):
+        """The BatchLoader of this stage's train_dataset, made on first use."""
         if getattr(self, "_loader", None) is None or self._loader.ds is not self.train_dataset:
             # decode + resize on host threads, flip + ColorJitter + normalize on the GPU
             # (pggan_amd.data; lib/dataset.py:106-117).  A new stage's loader replaces the
@@ -317,7 +322,7 @@ class ProgressiveGAN:
                                        gen=self._aug_gen,
                                        cache_bytes=None if gb is None else int(float(gb) * (1 << 30)),
                                        source_cache=getattr(self, "_source_cache", None))
-        return self._loader.next(idx, prefetch=self._order[nxt:nxt + B])
+        return self._loader
 
     def set_loss_collector(self):
         self._loss_collector = WGANGPLoss(self.args)
@@ -344,6 +349,82 @@ class ProgressiveGAN:
                 raise ValueError(f"msssim_pairs: {pairs} pairs need 2 * {pairs} of the swd_images = "
                                  f"{self._val['images']} images of a set")
             self._val["msssim_pairs"] = pairs
+        nq = cfg_get(self.args, "nn_queries", None)
+        if nq:          # blank: no nearest-neighbour search
+            nq = int(nq)
+            if nq < 1 or nq > self._val["images"]:
+                raise ValueError(f"nn_queries: {nq} queries need {nq} of the swd_images = "
+                                 f"{self._val['images']} images of a set")
+            self._val["nn_queries"] = nq
+            self._nn_settings()     # nn_k, nn_resolution: refused here, not at the first validation
+
+    def _nn_settings(self):
+        """(k, comparison resolution) of config `nn_k` (blank: 3) and `nn_resolution` (blank: 64)."""
+        from .metrics import NN_MAX_K
+        k = int(cfg_get(self.args, "nn_k", None) or 3)
+        if k < 1 or k > NN_MAX_K:
+            raise ValueError(f"nn_k: must be in [1, {NN_MAX_K}], got {k}")
+        rc = int(cfg_get(self.args, "nn_resolution", None) or 64)
+        if rc < 8 or rc > 128 or rc & (rc - 1):
+            raise ValueError(f"nn_resolution: must be a power of two in [8, 128], got {rc}")
+        return k, rc
+
+    def _nn_ops(self):
+        from . import _lib
+        ops = getattr(self, "_nn_ops_", None)
+        if ops is None:
+            ops = self._nn_ops_ = (type(self).ops_factory or _lib.HipOps)(torch.float32)
+        return ops
+
+    def _nn_database(self, nn):
+        """(rows int8 [N, D], sums int32 [N]) of every image of train_dataset at the stage size,
+        un-augmented (BatchLoader.raw_u8), or of the synthetic batch: built at the first use in
+        a stage and kept until reset_solver.  N * D bytes of device memory."""
+        key = (self.scale_index, nn.Rc)
+        db = getattr(self, "_nn_db", None)
+        if db is not None and db[0] == key:
+            return db[1], db[2]
+        if self.train_dataset is None:
+            if self.synthetic is None:
+                raise RuntimeError("nearest neighbours: no training images (set_dataset first)")
+            desc, sq = nn.descriptors(self.synthetic)
+        else:
+            loader, n = self._stage_loader(), len(self.train_dataset)
+            desc = torch.empty(n, nn.D, dtype=torch.int8, device=self.device)
+            sq = torch.empty(n, dtype=torch.int32, device=self.device)
+            for i in range(0, n, 64):
+                j = min(i + 64, n)
+                desc[i:j], sq[i:j] = nn.descriptors(loader.raw_u8(range(i, j)))
+        self._nn_db = (key, desc, sq)
+        return desc, sq
+
+    def _nn_images(self, idx):
+        """Training images idx (a list; -1: none, left grey) at the stage size, fp32 NCHW on the CPU."""
+        R = 4 * 2 ** self.scale_index
+        out = torch.zeros(len(idx), 3, R, R)
+        live = [k for k, i in enumerate(idx) if i >= 0]
+        if live and self.train_dataset is None:
+            out[live] = self.synthetic[[idx[k] for k in live]].float().cpu()
+        elif live:
+            u8 = self._stage_loader().raw_u8([idx[k] for k in live]).cpu()
+            out[live] = u8.permute(0, 3, 1, 2).float() / 127.5 - 1
+        return out
+
+    def nearest_neighbours(self, images, k=None):
+        """(idx, d2), int64 [Q, k]: the k training images nearest to each of `images` (fp32
+        [Q, 3, R, R] in [-1, 1] or uint8 [Q, R, R, 3] at the stage size R) in pixel space, at the
+        comparison resolution of config `nn_resolution` (pggan_amd.metrics.NearestNeighbours).
+        idx indexes train_dataset.paths (the synthetic batch with `synthetic_data`); slots
+        beyond the number of training images hold (-1, INT64_MAX).  k: default config `nn_k`."""
+        from .metrics import NearestNeighbours
+        R = 4 * 2 ** self.scale_index
+        k0, rc = self._nn_settings()
+        nn = NearestNeighbours(self._nn_ops(), R, k0 if k is None else k, min(rc, R))
+        nn.set_queries(images.to(self.device))
+        desc, sq = self._nn_database(nn)
+        nn.feed_descriptors(desc, sq, 0)
+        idx, d2 = nn.result()
+        return idx.clone(), d2.clone()
 
     def _valid_reals(self, R, n, B):
         """n validation reals at R x R as fp32 [-1, 1] batches of at most B: the images under
@@ -381,33 +462,55 @@ class ProgressiveGAN:
         With `msssim_pairs` the first 2 * msssim_pairs images of each set also go through
         MultiScaleSSIM: "msssim" (the generated images' mean pair similarity: lower is more
         diverse) and "msssim_real" (the data's own, what the former is read against) join the
-        dict, are printed, and appended to msssim.csv as step,scale,msssim,msssim_real."""
+        dict, are printed, and appended to msssim.csv as step,scale,msssim,msssim_real.
+        With `nn_queries` the first nn_queries images of each set are also searched for in the
+        training set (_nn_validation: "nn", "nn_real", "nn_min", nn.csv, nn/e{step}.jpg); that
+        part also runs at 8 x 8, where it is then the whole dict."""
         val = getattr(self, "_val", None)
         if val is None:
             return None
         master = cfg_get(self.args, "isMaster", False)
         R = 4 * 2 ** self.scale_index
-        if R < 16:
-            if master:
-                print(f"step {step}: SWD is undefined below 16x16 (stage is {R}x{R})")
+        nq = val.get("nn_queries")
+        if R < 16 and master:
+            print(f"step {step}: SWD is undefined below 16x16 (stage is {R}x{R})")
+        if nq and R < 8 and master:
+            print(f"step {step}: the nearest-neighbour search is undefined below 8x8 (stage is "
+                  f"{R}x{R})")
+        if R < 16 and not (nq and R >= 8):
             return None
         from . import _lib
         from .metrics import SlicedWasserstein
         ops = val.get("ops")
         if ops is None:
             ops = val["ops"] = (type(self).ops_factory or _lib.HipOps)(torch.float32)
-        n, B = val["images"], int(self.args.batch_per_gpu)
-        swd = SlicedWasserstein(ops, R, n, seed=val["seed"])
-        pairs = val.get("msssim_pairs")
+        # at 8x8 only the nearest-neighbour queries are drawn
+        n, B = val["images"] if R >= 16 else nq, int(self.args.batch_per_gpu)
+        swd = SlicedWasserstein(ops, R, n, seed=val["seed"]) if R >= 16 else None
+        pairs = val.get("msssim_pairs") if R >= 16 else None
         ms = None
         if pairs:       # the first 2 * pairs images of each set, as they pass by
             from .metrics import MultiScaleSSIM
             ms = {w: MultiScaleSSIM(ops, R, pairs) for w in ("real", "fake")}
+        nn = nn_q = None
+        if nq:          # the first nq images of each set, as rows at the comparison resolution
+            from .metrics import NearestNeighbours
+            k, rc = self._nn_settings()
+            nn = NearestNeighbours(ops, R, k, min(rc, R))
+            nn_q = {w: [] for w in ("real", "fake")}
+            nn_fakes = []       # the first 8 generated images, for the figure
 
         def feed(which, x):
-            swd.feed(which, x)
+            if swd is not None:
+                swd.feed(which, x)
             if ms is not None and ms[which].fed < 2 * pairs:
                 ms[which].feed(x[:2 * pairs - ms[which].fed])
+            if nn is not None:
+                have = sum(d.shape[0] for d, _ in nn_q[which])
+                if have < nq:
+                    nn_q[which].append(nn.descriptors(x[:nq - have]))
+                    if which == "fake" and have < 8:
+                        nn_fakes.append(x[:8 - have].detach().float().cpu())
 
         for x in self._valid_reals(R, n, B):
             feed("real", x)
@@ -415,16 +518,18 @@ class ProgressiveGAN:
         for i in range(0, n, B):     # always whole batches: one sampling engine shape
             z = torch.randn(B, self.args.latent_dim, generator=g).to(self.device)
             feed("fake", self.sample(z, ema=self.G_ema is not None)[:n - i])
-        out = swd.result()
-        levels = [out[k] for k in swd.sizes]
-        if master:
-            print(f"step {step}: SWD x1e3 " + " ".join(f"{k}:{out[k]:.4f}" for k in swd.sizes) +
-                  f" avg:{out['avg']:.4f}")
         d = f"{self.args.save_root}/{self.args.run_id}"
         os.makedirs(d, exist_ok=True)
-        with open(f"{d}/swd.csv", "a") as f:
-            f.write(",".join([str(step), str(self.scale_index)] +
-                             [repr(v) for v in levels + [out["avg"]]]) + "\n")
+        out = {}
+        if swd is not None:
+            out = swd.result()
+            levels = [out[k] for k in swd.sizes]
+            if master:
+                print(f"step {step}: SWD x1e3 " + " ".join(f"{k}:{out[k]:.4f}" for k in swd.sizes) +
+                      f" avg:{out['avg']:.4f}")
+            with open(f"{d}/swd.csv", "a") as f:
+                f.write(",".join([str(step), str(self.scale_index)] +
+                                 [repr(v) for v in levels + [out["avg"]]]) + "\n")
         if ms is not None:
             out["msssim"], out["msssim_real"] = ms["fake"].result(), ms["real"].result()
             if master:
@@ -432,6 +537,41 @@ class ProgressiveGAN:
             with open(f"{d}/msssim.csv", "a") as f:
                 f.write(",".join([str(step), str(self.scale_index), repr(out["msssim"]),
                                   repr(out["msssim_real"])]) + "\n")
+        if nn is not None:
+            out.update(self._nn_validation(nn, nn_q, torch.cat(nn_fakes), step, d, master))
+        return out
+
+    def _nn_validation(self, nn, queries, fakes, step, d, master):
+        """The nearest-neighbour part of validation(): `queries` {"real" / "fake": [(rows,
+        sums), ..]} against the stage's training images.  Returns {"nn", "nn_real"}: the median
+        over the queries of the RMS pixel distance (0..255 scale) to the nearest training
+        image, and "nn_min", the generated images' smallest: a generator that copies training
+        images shows as nn, nn_min far below nn_real, the held-out reals' own distance.
+        Appends step,scale,Rc,nn,nn_min,nn_real to nn.csv and writes nn/e{step}.jpg: the first
+        8 generated images in the top row, under each its k nearest training images."""
+        from PIL import Image
+        desc, sq = self._nn_database(nn)
+        near, res = {}, {}
+        for w in ("fake", "real"):
+            nn.set_query_descriptors(torch.cat([q for q, _ in queries[w]]),
+                                     torch.cat([s for _, s in queries[w]]))
+            nn.feed_descriptors(desc, sq, 0)
+            near[w] = nn.rms()[:, 0].cpu().numpy()
+            res[w] = nn.result()[0].cpu()
+        out = {"nn": float(np.median(near["fake"])), "nn_real": float(np.median(near["real"])),
+               "nn_min": float(near["fake"].min())}
+        if master:
+            print(f"step {step}: nearest training image at {nn.Rc}x{nn.Rc}, RMS of 255: median "
+                  f"{out['nn']:.3f} min {out['nn_min']:.3f} (reals {out['nn_real']:.3f})")
+        with open(f"{d}/nn.csv", "a") as f:
+            f.write(",".join([str(step), str(self.scale_index), str(nn.Rc), repr(out["nn"]),
+                              repr(out["nn_min"]), repr(out["nn_real"])]) + "\n")
+        idx = res["fake"][:fakes.shape[0]]
+        fakes = fakes[:idx.shape[0]]        # fewer than 8 queries: those
+        rows = [fakes] + [self._nn_images(idx[:, j].tolist()) for j in range(nn.k)]
+        grid = make_grid_image(rows).permute(1, 2, 0).numpy().astype(np.float64) * 255
+        os.makedirs(f"{d}/nn", exist_ok=True)
+        Image.fromarray(np.clip(np.rint(grid), 0, 255).astype(np.uint8)).save(f"{d}/nn/e{step}.jpg")
         return out
 
     # ------------------------------------------------------------------ step
@@ -676,6 +816,7 @@ class ProgressiveGAN:
     def reset_solver(self):
         """pggan/model.py:131-139."""
         self.flush()
+        self._nn_db = None       # the nearest-neighbour database of the stage that ends
         self.set_dataset()
         self.set_data_iterator()
         self.set_optimizers()
