@@ -516,6 +516,31 @@ int pg_nn_search(int Q, int N, int D, int k, const int8_t* q, const int* qsq, co
                  const int* dbsq, long long first_index, long long* best_d2, long long* best_idx,
                  void* ws, size_t ws_bytes, void* stream);
 
+/* ---- latent recovery: minimise a multi-scale pixel loss between G(z) and a target over z
+ * (DESIGN.md "Validation: latent recovery").
+ * pg_recon_loss: img, tgt, gimg fp32 NCHW [B][3][R][R] (16-byte aligned), R a power of two >= 4,
+ * 1 <= levels <= min(6, log2 R + 1), B <= 512.  With d = img - tgt and d_l its 2^l x 2^l box
+ * average (side R_l = R / 2^l):
+ *   loss[b] = sum_{l < levels} 1 / (3 R_l^2) sum_{c,y,x} d_l^2,   mse0[b] = the l = 0 term,
+ *   gimg[b][c][y][x] = d loss[b] / d img = 2 / (3 R^2) sum_{l < levels} d_l[c][y >> l][x >> l].
+ * One launch: both inputs read once, gimg written once, loss and mse0 WRITTEN (not accumulated)
+ * from per-workgroup partials summed in a fixed order through `scratch` (the stream's
+ * PG_SCRATCH_BYTES reduction scratch): no float atomics, bitwise repeatable. */
+int pg_recon_loss(int B, int R, int levels, const float* img, const float* tgt, float* gimg,
+                  float* loss, float* mse0, void* scratch, void* stream);
+/* One optimiser step on the latent rows z [B][Lz] (fp32; Lz a multiple of 64, at most 512), one
+ * wave per row, in this order:
+ *   1. if loss[b] < best_loss[b]: best_loss[b] = loss[b], best_z[b] = z[b] (loss: that of the
+ *      current z, as pg_recon_loss wrote it -- the loop reads nothing back per iteration);
+ *   2. gz = r (gzn - zn mean(zn gzn)), r = rsqrt(mean(z^2) + 1e-8), zn = z r: the PixelNorm
+ *      backward (lib/layers.py:8-14) of gzn [B][Lz], the gradient at zn = pixel_norm(z);
+ *   3. Adam on z with gz (m, v [B][Lz]; the 1-based `step`; pg_adam's update order; the
+ *      hyper-parameters are doubles, so 1 - beta is rounded to fp32 once, not beta first);
+ *   4. gz_out [B][Lz], if not NULL, = gz. */
+int pg_latent_step(int B, int Lz, float* z, const float* gzn, float* m, float* v, double lr,
+                   double beta1, double beta2, double eps, int step, const float* loss,
+                   float* best_loss, float* best_z, float* gz_out, void* stream);
+
 /* ---- stream ordering between the engine's streams (weight gradients on a side stream).
  * torch's cross-stream events record with a system-scope release: every record writes back and
  * invalidates the L2 of all XCDs and the next kernel on that stream starts ~6.5 us late.  The

@@ -89,6 +89,7 @@ _lib = None
 _SIDE_STREAMS = {}   # device index -> the least-priority side stream (pg_stream_create)
 
 _VP, _I, _F, _SZ, _U64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint64
+_D = ctypes.c_double
 _SIGS = {
     "pg_version": ([], _I),
     "pg_scratch_bytes": ([], _SZ),
@@ -168,6 +169,9 @@ _SIGS = {
     "pg_nn_workspace_bytes": ([_I, _I, _I], _SZ),
     "pg_nn_search": ([_I, _I, _I, _I, _VP, _VP, _VP, _VP, ctypes.c_longlong, _VP, _VP, _VP, _SZ,
                       _VP], _I),
+    "pg_recon_loss": ([_I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP], _I),
+    "pg_latent_step": ([_I, _I, _VP, _VP, _VP, _VP, _D, _D, _D, _D, _I, _VP, _VP, _VP, _VP, _VP],
+                       _I),
     "pg_step_plan_create": ([_I, _I, ctypes.POINTER(ctypes.c_int), _I, _I,
                              ctypes.POINTER(ctypes.c_void_p)], _I),
     "pg_step_plan_workspace_size": ([_VP], _SZ),
@@ -943,6 +947,40 @@ class HipOps:
         self._chk(self.lib.pg_nn_search(Q, N, D, k, _p(q), _p(qsq), _p(db), _p(dbsq),
                                         int(first_index), _p(best_d2), _p(best_idx), _p(ws),
                                         ws.numel(), self._s()), "nn_search")
+
+    # -- latent recovery (pggan_amd/recover.py, csrc/recover.hip) ----
+    def recon_loss(self, img, tgt, levels, gimg, loss, mse0):
+        """The multi-scale pixel loss between img and tgt (fp32 [B,3,R,R]) over `levels` box
+        pyramids: loss [B], its level-0 term mse0 [B] and gimg = d loss / d img, in one launch
+        (pg_recon_loss)."""
+        self._cuda_named("recon_loss", img, tgt, gimg, loss, mse0)
+        B, R = img.shape[0], img.shape[-1]
+        for t in (img, tgt, gimg):
+            if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (B, 3, R, R):
+                raise RuntimeError("pggan_amd: recon_loss takes contiguous fp32 [B,3,R,R] images, "
+                                   f"got {t.dtype} {tuple(t.shape)}")
+        for t in (loss, mse0):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != B:
+                raise RuntimeError(f"pggan_amd: recon_loss writes fp32 [{B}] sums")
+        self._chk(self.lib.pg_recon_loss(B, R, int(levels), _p(img), _p(tgt), _p(gimg), _p(loss),
+                                         _p(mse0), self._scr(), self._s()), "recon_loss")
+
+    def latent_step(self, z, gzn, m, v, *, lr, beta1, beta2, eps, step, loss, best_loss, best_z,
+                    gz_out=None):
+        """One Adam step on the latents z [B,Lz] from gzn, the gradient at pixel_norm(z), after
+        recording (loss, z) as the best where loss < best_loss (pg_latent_step)."""
+        self._cuda_named("latent_step", z, gzn, m, v, loss, best_loss, best_z, gz_out)
+        B, Lz = z.shape
+        for t in (z, gzn, m, v, best_z, gz_out):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or
+                                  tuple(t.shape) != (B, Lz)):
+                raise RuntimeError(f"pggan_amd: latent_step takes contiguous fp32 [{B}, {Lz}] rows")
+        for t in (loss, best_loss):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != B:
+                raise RuntimeError(f"pggan_amd: latent_step takes fp32 [{B}] losses")
+        self._chk(self.lib.pg_latent_step(B, Lz, _p(z), _p(gzn), _p(m), _p(v), lr, beta1, beta2, eps,
+                                          int(step), _p(loss), _p(best_loss), _p(best_z),
+                                          _p(gz_out), self._s()), "latent_step")
 
     def cast(self, x, y):
         self._cuda(x, y)

@@ -385,6 +385,7 @@ class StepEngine:
             g["gz0"] = t(B, 4, 4, d[0])
             g["gh0"] = t(B, 4, 4, d[0])
             g["gzf"] = t(B, 4, 4, d[0])
+            g["gzn"] = t(B, self.latent, f32=True)      # dL/d pixel_norm(z) (g_input_grad)
         B = B0
         self.g2 = self.g_hi = None
         if merge_g and need_G:
@@ -886,7 +887,10 @@ class StepEngine:
         self.ops.rgb_out(self._ylvl(s), w, P[f"toRGB_blocks.{s}.toRGB.module.bias"], he(d[s]),
                          g["img"], B=self.B, R=self.R, C=d[s], **kw)   # nets.py:140-156
 
-    def g_backward(self, P, GR, gimg, alpha):
+    def g_backward(self, P, GR, gimg, alpha, wgrads=True, gzn=None):
+        """wgrads=False: the input-gradient chain alone -- no weight or bias gradient is
+        launched and GR is not read (g_input_grad).  gzn: also write the gradient at
+        zn = pixel_norm(z), fp32 [B, latent], the latent format layer's input gradient."""
         ops, g, d, s, B = self.ops, self.g, self.depths, self.s, self.B
         self._side_join("G")
         kw = {}
@@ -894,8 +898,8 @@ class StepEngine:
         if low:
             pre = f"toRGB_blocks.{s - 1}.toRGB.module."
             kw = dict(xp=self._ylvl(s - 1), wp=P[pre + "weight"], cp=he(d[s - 1]), Cp=d[s - 1],
-                      alpha=alpha, gxp=g[f"gy{s - 1}"], dwp=GR[pre + "weight"],
-                      dbp=GR[pre + "bias"])
+                      alpha=alpha, gxp=g[f"gy{s - 1}"], dwp=GR[pre + "weight"] if wgrads else None,
+                      dbp=GR[pre + "bias"] if wgrads else None)
         pre = f"toRGB_blocks.{s}.toRGB.module."
         # the toRGB input gradient with the top block's PixelNorm backward fused in
         # (pg_rgb_out_bwd_pn: the 16-channel 1024^2 dL/dy never goes through HBM); its weight
@@ -906,7 +910,7 @@ class StepEngine:
         w_rgb = P[pre + "weight"]
         # the toRGB weight gradient in the same pass as the input gradient where the fused form
         # runs (y and gimg streamed once, on the main stream: rgb_dgrad_pn_wg_v)
-        wg_fused = top_pn and self.fuse_torgb_wg
+        wg_fused = top_pn and self.fuse_torgb_wg and wgrads
         if top_pn:
             ops.rgb_out_bwd_pn(self._ylvl(s), g[f"rb{s - 1}"], w_rgb, he(d[s]), gimg,
                                g[f"gzb{s - 1}"], B=B, R=self.R, C=d[s], slope=SLOPE,
@@ -917,7 +921,7 @@ class StepEngine:
                             **{k: (None if k in ("dwp", "dbp") else v) for k, v in kw.items()})
         if wg_fused:
             self._ready_main("G", pre)
-        else:
+        elif wgrads:
             # img / the fade-in branch's operands are D / G buffers: pending for both nets
             self._side_call(("G", "D"), ops.rgb_out_bwd, self._ylvl(s), w_rgb, he(d[s]), gimg, None,
                             GR[pre + "weight"], GR[pre + "bias"], B=B, R=self.R, C=d[s],
@@ -930,10 +934,11 @@ class StepEngine:
             if pn_done != i:
                 self._g_pn_bwd(f"b{i}", g[f"ub{i}"], g[f"yb{i}"], g[f"rb{i}"], g[f"gy{i + 1}"],
                                g[f"gzb{i}"], Ri, d[i + 1], d[i + 1], L.CONV_LRELU)
-            self._wgrad("G", f"b{i}", g[f"ya{i}"], g[f"gzb{i}"], GR[b + "weight"], Ri, d[i + 1],
-                        d[i + 1],
-                        db=GR[b + "bias"])
-            self._ready("G", b)
+            if wgrads:
+                self._wgrad("G", f"b{i}", g[f"ya{i}"], g[f"gzb{i}"], GR[b + "weight"], Ri, d[i + 1],
+                            d[i + 1],
+                            db=GR[b + "bias"])
+                self._ready("G", b)
             if self._pnb_fused(Ri, d[i], d[i + 1]):
                 # conv b's input gradient with conv a's PixelNorm + LReLU backward in its
                 # epilogue (the gradient w.r.t. ya never goes through HBM)
@@ -944,10 +949,11 @@ class StepEngine:
                            dgrad=True)
                 self._g_pn_bwd(f"a{i}", g[f"ua{i}"], g[f"ya{i}"], g[f"ra{i}"], g[f"gya{i}"],
                                g[f"gza{i}"], Ri, d[i], d[i + 1], L.CONV_UPS_IN | L.CONV_LRELU)
-            self._wgrad("G", f"a{i}", self._ylvl(i), g[f"gza{i}"], GR[a + "weight"], Ri, d[i],
-                        d[i + 1], ups=True,
-                        db=GR[a + "bias"])
-            self._ready("G", a)
+            if wgrads:
+                self._wgrad("G", f"a{i}", self._ylvl(i), g[f"gza{i}"], GR[a + "weight"], Ri, d[i],
+                            d[i + 1], ups=True,
+                            db=GR[a + "bias"])
+                self._ready("G", a)
             # level s-1 also received the toRGB fade-in branch's gradient: accumulate
             flags = L.CONV_POOL | (L.CONV_ACCUM if (i == s - 1 and low) else 0)
             if not (flags & L.CONV_ACCUM) and self._pn_pool(i):
@@ -965,15 +971,22 @@ class StepEngine:
         # the input-gradient chain ends at the latent: with tail_main the last two weight
         # gradients run on the main stream after it while the side stream drains its queue
         tail = self._tail_main_on()
-        if not tail:
+        if wgrads and not tail:
             self._wgrad("G", "first", g["h0"], g["gz0"], GR[fb + "weight"], 4, d[0], d[0],
                         db=GR[fb + "bias"])
             self._ready("G", fb)
         self._conv("G", "first", g["gz0"], g["gh0"], 4, d[0], d[0], 0, dgrad=True)
         ops.pixnorm_lrelu_bwd(g["f"], g["gh0"], g["gzf"], d[0], self.hyper.slope_cfg)
+        lkw = dict(B=B, flags=L.LIN_OUT_CHW, scale=he(self.latent))
+        if gzn is not None:
+            # the latent format layer's input gradient (nets.py:129-130), fp32 whatever the
+            # storage dtype; its PixelNorm backward is the caller's (pg_latent_step, or
+            # pixnorm_lrelu_bwd(mask=False))
+            ops.linear_dgrad(g["gzf"], P["latent_format_layer.module.weight"], gzn, **lkw)
+        if not wgrads:
+            return
         lin = (g["zn"], g["gzf"], GR["latent_format_layer.module.weight"],
                GR["latent_format_layer.module.bias"])
-        lkw = dict(B=B, flags=L.LIN_OUT_CHW, scale=he(self.latent))
         if tail:
             self._wgrad("G", "first", g["h0"], g["gz0"], GR[fb + "weight"], 4, d[0], d[0],
                         db=GR[fb + "bias"], main=True)
@@ -982,6 +995,13 @@ class StepEngine:
         else:
             self._side_call(("G",), ops.linear_wgrad, *lin, **lkw)
             self._ready("G", "latent_format_layer.module.")
+
+    def g_input_grad(self, P, gimg, alpha):
+        """dL/d pixel_norm(z) from gimg = dL/dimg of the last g_forward(keep=True): g_backward's
+        input-gradient chain without any weight or bias gradient, then the latent format
+        layer's input gradient.  Returns g["gzn"], fp32 [B, latent]."""
+        self.g_backward(P, None, gimg, alpha, wgrads=False, gzn=self.g["gzn"])
+        return self.g["gzn"]
 
     # ================================================================== D
     def d_forward(self, P, img, alpha, join=True):

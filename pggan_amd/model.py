@@ -20,7 +20,8 @@ Differences (deliberate):
   * config `use_validation` fills in the reference's empty validation(): the paper's sliced
     Wasserstein distance on the held-out 30 % of the images (pggan_amd.metrics); config
     `msssim_pairs` (blank: off) adds the paper's MS-SSIM between pairs of generated images,
-    `nn_queries` (blank: off) the distance to the nearest training images.
+    `nn_queries` (blank: off) the distance to the nearest training images, `recover_images`
+    (blank: off) latent recovery of training, held-out and generated images (also `recover()`).
 """
 from __future__ import annotations
 
@@ -357,6 +358,26 @@ class ProgressiveGAN:
                                  f"{self._val['images']} images of a set")
             self._val["nn_queries"] = nq
             self._nn_settings()     # nn_k, nn_resolution: refused here, not at the first validation
+        nr = cfg_get(self.args, "recover_images", None)
+        if nr:          # blank: no latent recovery
+            nr = int(nr)
+            if nr < 1 or nr > self._val["images"]:
+                raise ValueError(f"recover_images: {nr} targets need {nr} of the swd_images = "
+                                 f"{self._val['images']} images of a set")
+            self._val["recover_images"] = nr
+            self._recover_settings()
+
+    def _recover_settings(self):
+        """recover_latents' keywords from config `recover_steps` (blank: 200), `recover_lr`
+        (blank: 0.1) and `recover_levels` (blank: the module's default for the stage)."""
+        steps = int(cfg_get(self.args, "recover_steps", None) or 200)
+        lr = float(cfg_get(self.args, "recover_lr", None) or 0.1)
+        levels = cfg_get(self.args, "recover_levels", None)
+        if steps < 1 or not lr > 0:
+            raise ValueError(f"recover_steps / recover_lr: must be positive, got {steps} / {lr}")
+        if levels is not None and levels != "" and not 1 <= int(levels) <= 6:
+            raise ValueError(f"recover_levels: must be in [1, 6], got {levels}")
+        return dict(steps=steps, lr=lr, levels=int(levels) if levels not in (None, "") else None)
 
     def _nn_settings(self):
         """(k, comparison resolution) of config `nn_k` (blank: 3) and `nn_resolution` (blank: 64)."""
@@ -465,19 +486,26 @@ class ProgressiveGAN:
         dict, are printed, and appended to msssim.csv as step,scale,msssim,msssim_real.
         With `nn_queries` the first nn_queries images of each set are also searched for in the
         training set (_nn_validation: "nn", "nn_real", "nn_min", nn.csv, nn/e{step}.jpg); that
-        part also runs at 8 x 8, where it is then the whole dict."""
+        part also runs at 8 x 8, where it is then the whole dict.
+        With `recover_images` the first recover_images training images, held-out reals and
+        generated images are recovered from the generator (_recover_validation: "rec_train",
+        "rec_real", "rec_fake", recover.csv, recover/e{step}.jpg), on the master, at every
+        stage."""
         val = getattr(self, "_val", None)
         if val is None:
             return None
         master = cfg_get(self.args, "isMaster", False)
         R = 4 * 2 ** self.scale_index
         nq = val.get("nn_queries")
+        nr = val.get("recover_images") if master else None
         if R < 16 and master:
             print(f"step {step}: SWD is undefined below 16x16 (stage is {R}x{R})")
         if nq and R < 8 and master:
             print(f"step {step}: the nearest-neighbour search is undefined below 8x8 (stage is "
                   f"{R}x{R})")
-        if R < 16 and not (nq and R >= 8):
+        if R < 8:
+            nq = None
+        if R < 16 and not nq and not nr:
             return None
         from . import _lib
         from .metrics import SlicedWasserstein
@@ -485,7 +513,7 @@ class ProgressiveGAN:
         if ops is None:
             ops = val["ops"] = (type(self).ops_factory or _lib.HipOps)(torch.float32)
         # at 8x8 only the nearest-neighbour queries are drawn
-        n, B = val["images"] if R >= 16 else nq, int(self.args.batch_per_gpu)
+        n, B = val["images"] if R >= 16 else max(nq or 0, nr or 0), int(self.args.batch_per_gpu)
         swd = SlicedWasserstein(ops, R, n, seed=val["seed"]) if R >= 16 else None
         pairs = val.get("msssim_pairs") if R >= 16 else None
         ms = None
@@ -499,8 +527,13 @@ class ProgressiveGAN:
             nn = NearestNeighbours(ops, R, k, min(rc, R))
             nn_q = {w: [] for w in ("real", "fake")}
             nn_fakes = []       # the first 8 generated images, for the figure
+        rec_t = {w: [] for w in ("real", "fake")} if nr else None   # the first nr images of each set
 
         def feed(which, x):
+            if rec_t is not None:
+                have = sum(t.shape[0] for t in rec_t[which])
+                if have < nr:
+                    rec_t[which].append(x[:nr - have].detach().float().cpu())
             if swd is not None:
                 swd.feed(which, x)
             if ms is not None and ms[which].fed < 2 * pairs:
@@ -539,6 +572,89 @@ class ProgressiveGAN:
                                   repr(out["msssim_real"])]) + "\n")
         if nn is not None:
             out.update(self._nn_validation(nn, nn_q, torch.cat(nn_fakes), step, d, master))
+        if rec_t is not None:
+            out.update(self._recover_validation({w: torch.cat(t) for w, t in rec_t.items()}, step, d))
+        return out
+
+    def recover(self, images, fade=True, **kw):
+        """Latent recovery (pggan_amd.recover.recover_latents): (z, loss, mse0, reconstructions)
+        for `images`, fp32 [N, 3, R, R] in [-1, 1] or uint8 [N, R, R, 3] at the stage size R, from
+        the averaged generator when the weight average is on, else from G, at G's current
+        alpha.  The targets get the training reals' fade (pggan/model.py:217-221), so during a
+        fade-in the generator is asked for what it is trained to produce (fade=False: targets that
+        are the generator's own output already).  kw: recover_latents'
+        (steps, lr, levels, seed, z0, betas, batch).  Runs on buffers of its own: the training
+        engine, the RNG offsets and the optimiser state are not touched."""
+        from .recover import recover_latents
+        self.flush()
+        net = self.G
+        if self.G_ema is not None:
+            net = self.G_ema
+            net.alpha = self.G.alpha
+        R = 4 * 2 ** self.scale_index
+        x = images.to(self.device)
+        if x.dtype == torch.uint8 and x.dim() == 4 and x.shape[3] == 3:
+            x = x.permute(0, 3, 1, 2).float() / 127.5 - 1
+        if x.dim() != 4 or tuple(x.shape[1:]) != (3, R, R):
+            raise ValueError(f"recover: images must be fp32 [N, 3, {R}, {R}] or uint8 [N, {R}, {R}, 3], "
+                             f"got {images.dtype} {tuple(images.shape)}")
+        x = x.float().contiguous()
+        alpha = float(net.alpha)
+        if fade and self.scale_index >= 1 and alpha != 1.0:
+            faded = torch.empty_like(x)
+            self._nn_ops().img_fade(x, alpha, faded)
+            x = faded
+        return recover_latents(net, x, **kw)
+
+    def _recover_validation(self, sets, step, d):
+        """The latent-recovery part of validation(): `sets` {"real" / "fake": fp32 [N, 3, R, R]
+        on the host}, the held-out reals and the generator's own samples; the training set's
+        first N images are fetched here, un-augmented.  Returns {"rec_train", "rec_real",
+        "rec_fake"}: the median over each set of sqrt(mse0) * 127.5, the RMS reconstruction error
+        on the 0..255 scale nn.csv uses.  rec_fake calibrates the optimiser (the generator can
+        produce its own samples: if this is not near zero the search fails, not the
+        generator); rec_train far below rec_real is memorisation.  Appends
+        step,scale,steps,levels,rec_train,rec_real,rec_fake to recover.csv and writes
+        recover/e{step}.jpg: the first 8 training targets, their reconstructions, the first 8
+        held-out targets, their reconstructions."""
+        from PIL import Image
+        from .recover import default_levels
+        kw = self._recover_settings()
+        # the starting latents come from seed + 2: not the draws (seed) behind the generated set
+        n = sets["real"].shape[0]
+        R = 4 * 2 ** self.scale_index
+        if kw["levels"] is None:
+            kw["levels"] = default_levels(R)
+        kw["levels"] = min(kw["levels"], int(math.log2(R)) + 1)
+        if self.train_dataset is None:
+            if self.synthetic is None:
+                raise RuntimeError("latent recovery: no training images (set_dataset first)")
+            sets["train"] = self.synthetic[[j % self.synthetic.shape[0] for j in range(n)]].float()
+        else:
+            idx = [j % len(self.train_dataset) for j in range(n)]
+            sets["train"] = self._stage_loader().raw_u8(idx)
+        out, shown = {}, {}
+        for w in ("train", "real", "fake"):
+            _, _, mse0, img = self.recover(sets[w], fade=w != "fake",
+                                           batch=int(self.args.batch_per_gpu),
+                                           seed=self._val["seed"] + 2, **kw)
+            out[f"rec_{w}"] = float(np.median(np.sqrt(mse0.double().cpu().numpy()) * 127.5))
+            shown[w] = img[:8].float().cpu()
+        print(f"step {step}: latent recovery, {kw['steps']} steps, {kw['levels']} levels, RMS of 255: "
+              f"train {out['rec_train']:.3f} held-out {out['rec_real']:.3f} "
+              f"generated {out['rec_fake']:.3f}")
+        with open(f"{d}/recover.csv", "a") as f:
+            f.write(",".join([str(step), str(self.scale_index), str(kw["steps"]), str(kw["levels"]),
+                              repr(out["rec_train"]), repr(out["rec_real"]),
+                              repr(out["rec_fake"])]) + "\n")
+        tr = sets["train"][:8]
+        if tr.dtype == torch.uint8:
+            tr = tr.permute(0, 3, 1, 2).float() / 127.5 - 1
+        rows = [tr.float().cpu(), shown["train"], sets["real"][:8], shown["real"]]
+        grid = make_grid_image(rows).permute(1, 2, 0).numpy().astype(np.float64) * 255
+        os.makedirs(f"{d}/recover", exist_ok=True)
+        Image.fromarray(np.clip(np.rint(grid), 0, 255).astype(np.uint8)).save(
+            f"{d}/recover/e{step}.jpg")
         return out
 
     def _nn_validation(self, nn, queries, fakes, step, d, master):

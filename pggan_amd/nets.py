@@ -132,9 +132,11 @@ def _check_version(ctx):
 
 
 class _GFn(torch.autograd.Function):
-    """Generator forward / first-order backward on the HIP kernels (pggan/nets.py:121-161;
-    the gradient w.r.t. every parameter; the latent receives none, as in the reference
-    where z never requires grad)."""
+    """Generator forward / first-order backward on the HIP kernels (pggan/nets.py:121-161):
+    the gradient w.r.t. every parameter and, for a z that requires grad, dL/dz (latent
+    recovery, pggan_amd.recover; in the reference's training z never requires grad).  With
+    only z requiring grad the backward is the input-gradient pass alone
+    (StepEngine.g_input_grad): no weight gradient is launched."""
 
     @staticmethod
     def forward(ctx, module, z, *params):
@@ -146,6 +148,7 @@ class _GFn(torch.autograd.Function):
         eng.fwd_version += 1
         ctx.eng, ctx.version, ctx.names, ctx.alpha = eng, eng.fwd_version, names, float(module.alpha)
         ctx.P = P
+        ctx.z_like = (z.shape, z.dtype)
         eng.pack("G", P)
         return eng.g_forward(P, z.reshape(z.shape[0], -1).float(), ctx.alpha).clone()
 
@@ -153,10 +156,21 @@ class _GFn(torch.autograd.Function):
     def backward(ctx, gimg):
         _no_double_backward()
         _check_version(ctx)
-        GR = {n: torch.zeros_like(p) for n, p in ctx.P.items()}
-        ctx.eng.g_backward(ctx.P, GR, gimg.float().contiguous(), ctx.alpha)
-        dead = E.dead_params("G", ctx.eng.s)     # unused at this stage: grad None, as in torch
-        return (None, None) + tuple(None if n in dead else GR[n] for n in ctx.names)
+        eng = ctx.eng
+        want_z, want_p = ctx.needs_input_grad[1], any(ctx.needs_input_grad[2:])
+        GR = {n: torch.zeros_like(p) for n, p in ctx.P.items()} if want_p else None
+        eng.g_backward(ctx.P, GR, gimg.float().contiguous(), ctx.alpha, wgrads=want_p,
+                       gzn=eng.g["gzn"] if want_z else None)
+        dz = None
+        if want_z:
+            # through zn = pixel_norm(z) (nets.py:124-125); g["z"] still holds this forward's z
+            dz = torch.empty_like(eng.g["gzn"])
+            eng.ops.pixnorm_lrelu_bwd(eng.g["z"], eng.g["gzn"], dz, eng.latent, 1.0, mask=False)
+            dz = dz.reshape(ctx.z_like[0]).to(ctx.z_like[1])
+        if not want_p:
+            return (None, dz) + (None,) * len(ctx.names)
+        dead = E.dead_params("G", eng.s)         # unused at this stage: grad None, as in torch
+        return (None, dz) + tuple(None if n in dead else GR[n] for n in ctx.names)
 
 
 class _DFn(torch.autograd.Function):
@@ -237,7 +251,8 @@ class Generator(nn.Module):
 
     def forward(self, x):
         """pggan/nets.py:121-161 on the HIP kernels.  Differentiable once when grad is
-        enabled and a parameter requires it (_GFn); a forward-only engine otherwise."""
+        enabled and a parameter or the latent requires it (_GFn); a forward-only engine
+        otherwise."""
         if _wants_grad(x, self):
             return _GFn.apply(self, x, *self.parameters())
         s = self.scale_index

@@ -87,6 +87,8 @@ for step in "$@"; do
     dp) run dp 600 python -u -m pytest tests/test_gpu_dp.py -x -q --timeout 300 --timeout-method thread ;;
     graph) run graph 600 python -u -m pytest tests/test_gpu_graph.py -x -q --timeout 300 --timeout-method thread ;;
     loader) run loader 600 python tools/loader_bench.py --out $OUT/loader.json ;;
+    recover) run recover 600 python -u -m pytest tests/test_gpu_recover.py -q -s ;;
+    recoverb) run recoverb 900 python tools/recover_bench.py --json $OUT/recover_bench.json ;;
     configs) run configs 1500 bash tools/configs_bench.sh ;;
     rehearsal) run rehearsal 900 bash tools/dp_rehearsal.sh ;;
     *) echo "unknown step $step"; exit 2 ;;
