@@ -38,6 +38,7 @@ from .config import cfg_get
 from .data import BatchLoader, HbmSourceCache, ImageFolderDataset
 from .loss import WGANGPLoss
 from .nets import Discriminator, Generator
+from .validation import Validation
 
 
 class FlatAdam:
@@ -139,6 +140,7 @@ class ProgressiveGAN:
         self.train_dataset = None
         self.synthetic = None
         self._exchange = None
+        self._validation = Validation(self)
 
     # ------------------------------------------------------------------ models
     def initialize_models(self):
@@ -333,103 +335,14 @@ class ProgressiveGAN:
         return self._loss_collector
 
     # ------------------------------------------------------------------ validation
+    # (pggan_amd.validation: the settings, the parts, their shared state)
     def set_validation(self):
         """Config `use_validation`: the paper's sliced Wasserstein distance between `swd_images`
         reals and as many generated images (pggan_amd.metrics), every `valid_cycle` steps; with
         `msssim_pairs` also the paper's MS-SSIM over that many pairs of the same images."""
-        self._val = None
-        if not cfg_get(self.args, "use_validation", False):
-            return
-        self._val = dict(images=int(cfg_get(self.args, "swd_images", None) or 4096),
-                         seed=int(cfg_get(self.args, "swd_seed", None) or 0))
-        self.valid_cycle = int(cfg_get(self.args, "valid_cycle", None) or self.args.ckpt_cycle)
-        pairs = cfg_get(self.args, "msssim_pairs", None)
-        if pairs:       # blank: no MS-SSIM
-            pairs = int(pairs)
-            if pairs < 1 or 2 * pairs > self._val["images"]:
-                raise ValueError(f"msssim_pairs: {pairs} pairs need 2 * {pairs} of the swd_images = "
-                                 f"{self._val['images']} images of a set")
-            self._val["msssim_pairs"] = pairs
-        nq = cfg_get(self.args, "nn_queries", None)
-        if nq:          # blank: no nearest-neighbour search
-            nq = int(nq)
-            if nq < 1 or nq > self._val["images"]:
-                raise ValueError(f"nn_queries: {nq} queries need {nq} of the swd_images = "
-                                 f"{self._val['images']} images of a set")
-            self._val["nn_queries"] = nq
-            self._nn_settings()     # nn_k, nn_resolution: refused here, not at the first validation
-        nr = cfg_get(self.args, "recover_images", None)
-        if nr:          # blank: no latent recovery
-            nr = int(nr)
-            if nr < 1 or nr > self._val["images"]:
-                raise ValueError(f"recover_images: {nr} targets need {nr} of the swd_images = "
-                                 f"{self._val['images']} images of a set")
-            self._val["recover_images"] = nr
-            self._recover_settings()
-
-    def _recover_settings(self):
-        """recover_latents' keywords from config `recover_steps` (blank: 200), `recover_lr`
-        (blank: 0.1) and `recover_levels` (blank: the module's default for the stage)."""
-        steps = int(cfg_get(self.args, "recover_steps", None) or 200)
-        lr = float(cfg_get(self.args, "recover_lr", None) or 0.1)
-        levels = cfg_get(self.args, "recover_levels", None)
-        if steps < 1 or not lr > 0:
-            raise ValueError(f"recover_steps / recover_lr: must be positive, got {steps} / {lr}")
-        if levels is not None and levels != "" and not 1 <= int(levels) <= 6:
-            raise ValueError(f"recover_levels: must be in [1, 6], got {levels}")
-        return dict(steps=steps, lr=lr, levels=int(levels) if levels not in (None, "") else None)
-
-    def _nn_settings(self):
-        """(k, comparison resolution) of config `nn_k` (blank: 3) and `nn_resolution` (blank: 64)."""
-        from .metrics import NN_MAX_K
-        k = int(cfg_get(self.args, "nn_k", None) or 3)
-        if k < 1 or k > NN_MAX_K:
-            raise ValueError(f"nn_k: must be in [1, {NN_MAX_K}], got {k}")
-        rc = int(cfg_get(self.args, "nn_resolution", None) or 64)
-        if rc < 8 or rc > 128 or rc & (rc - 1):
-            raise ValueError(f"nn_resolution: must be a power of two in [8, 128], got {rc}")
-        return k, rc
-
-    def _nn_ops(self):
-        from . import _lib
-        ops = getattr(self, "_nn_ops_", None)
-        if ops is None:
-            ops = self._nn_ops_ = (type(self).ops_factory or _lib.HipOps)(torch.float32)
-        return ops
-
-    def _nn_database(self, nn):
-        """(rows int8 [N, D], sums int32 [N]) of every image of train_dataset at the stage size,
-        un-augmented (BatchLoader.raw_u8), or of the synthetic batch: built at the first use in
-        a stage and kept until reset_solver.  N * D bytes of device memory."""
-        key = (self.scale_index, nn.Rc)
-        db = getattr(self, "_nn_db", None)
-        if db is not None and db[0] == key:
-            return db[1], db[2]
-        if self.train_dataset is None:
-            if self.synthetic is None:
-                raise RuntimeError("nearest neighbours: no training images (set_dataset first)")
-            desc, sq = nn.descriptors(self.synthetic)
-        else:
-            loader, n = self._stage_loader(), len(self.train_dataset)
-            desc = torch.empty(n, nn.D, dtype=torch.int8, device=self.device)
-            sq = torch.empty(n, dtype=torch.int32, device=self.device)
-            for i in range(0, n, 64):
-                j = min(i + 64, n)
-                desc[i:j], sq[i:j] = nn.descriptors(loader.raw_u8(range(i, j)))
-        self._nn_db = (key, desc, sq)
-        return desc, sq
-
-    def _nn_images(self, idx):
-        """Training images idx (a list; -1: none, left grey) at the stage size, fp32 NCHW on the CPU."""
-        R = 4 * 2 ** self.scale_index
-        out = torch.zeros(len(idx), 3, R, R)
-        live = [k for k, i in enumerate(idx) if i >= 0]
-        if live and self.train_dataset is None:
-            out[live] = self.synthetic[[idx[k] for k in live]].float().cpu()
-        elif live:
-            u8 = self._stage_loader().raw_u8([idx[k] for k in live]).cpu()
-            out[live] = u8.permute(0, 3, 1, 2).float() / 127.5 - 1
-        return out
+        settings = self._validation.configure()
+        if settings is not None:
+            self.valid_cycle = settings.valid_cycle
 
     def nearest_neighbours(self, images, k=None):
         """(idx, d2), int64 [Q, k]: the k training images nearest to each of `images` (fp32
@@ -437,42 +350,7 @@ class ProgressiveGAN:
         comparison resolution of config `nn_resolution` (pggan_amd.metrics.NearestNeighbours).
         idx indexes train_dataset.paths (the synthetic batch with `synthetic_data`); slots
         beyond the number of training images hold (-1, INT64_MAX).  k: default config `nn_k`."""
-        from .metrics import NearestNeighbours
-        R = 4 * 2 ** self.scale_index
-        k0, rc = self._nn_settings()
-        nn = NearestNeighbours(self._nn_ops(), R, k0 if k is None else k, min(rc, R))
-        nn.set_queries(images.to(self.device))
-        desc, sq = self._nn_database(nn)
-        nn.feed_descriptors(desc, sq, 0)
-        idx, d2 = nn.result()
-        return idx.clone(), d2.clone()
-
-    def _valid_reals(self, R, n, B):
-        """n validation reals at R x R as fp32 [-1, 1] batches of at most B: the images under
-        `valid_dataset_root`, else the held-out 30 % of set_dataset, decoded like the training
-        images without flip or jitter (wrapping around a shorter list); with `synthetic_data`
-        fresh U[-1, 1) draws.  Nothing here is shared with the training loader."""
-        root = cfg_get(self.args, "valid_dataset_root", None)
-        if root:
-            from .data import image_paths
-            paths = sorted(image_paths([root]))
-            if not paths:
-                raise RuntimeError(f"valid_dataset_root: no images under {root}")
-        else:
-            paths = list(getattr(self, "valid_paths", None) or [])
-        if paths:
-            from .data import load_u8
-            for i in range(0, n, B):
-                u8 = np.stack([load_u8(paths[j % len(paths)], R) for j in range(i, min(i + B, n))])
-                x = torch.from_numpy(u8).permute(0, 3, 1, 2).float() / 127.5 - 1
-                yield x.contiguous().to(self.device)
-        elif cfg_get(self.args, "synthetic_data", False):
-            g = torch.Generator().manual_seed(self._val["seed"] + 1)
-            for i in range(0, n, B):
-                yield (torch.rand(min(B, n - i), 3, R, R, generator=g) * 2 - 1).to(self.device)
-        else:
-            raise RuntimeError("validation: no real images (set valid_dataset_root, or train on "
-                               "a dataset so that its held-out 30 % is used)")
+        return self._validation.nearest_neighbours(images, k)
 
     def validation(self, step=0):
         """Sliced Wasserstein distance x 1e3 per Laplacian level between reals and images of
@@ -485,96 +363,13 @@ class ProgressiveGAN:
         diverse) and "msssim_real" (the data's own, what the former is read against) join the
         dict, are printed, and appended to msssim.csv as step,scale,msssim,msssim_real.
         With `nn_queries` the first nn_queries images of each set are also searched for in the
-        training set (_nn_validation: "nn", "nn_real", "nn_min", nn.csv, nn/e{step}.jpg); that
+        training set (validation.NnPart: "nn", "nn_real", "nn_min", nn.csv, nn/e{step}.jpg); that
         part also runs at 8 x 8, where it is then the whole dict.
         With `recover_images` the first recover_images training images, held-out reals and
-        generated images are recovered from the generator (_recover_validation: "rec_train",
+        generated images are recovered from the generator (validation.RecoverPart: "rec_train",
         "rec_real", "rec_fake", recover.csv, recover/e{step}.jpg), on the master, at every
         stage."""
-        val = getattr(self, "_val", None)
-        if val is None:
-            return None
-        master = cfg_get(self.args, "isMaster", False)
-        R = 4 * 2 ** self.scale_index
-        nq = val.get("nn_queries")
-        nr = val.get("recover_images") if master else None
-        if R < 16 and master:
-            print(f"step {step}: SWD is undefined below 16x16 (stage is {R}x{R})")
-        if nq and R < 8 and master:
-            print(f"step {step}: the nearest-neighbour search is undefined below 8x8 (stage is "
-                  f"{R}x{R})")
-        if R < 8:
-            nq = None
-        if R < 16 and not nq and not nr:
-            return None
-        from . import _lib
-        from .metrics import SlicedWasserstein
-        ops = val.get("ops")
-        if ops is None:
-            ops = val["ops"] = (type(self).ops_factory or _lib.HipOps)(torch.float32)
-        # at 8x8 only the nearest-neighbour queries are drawn
-        n, B = val["images"] if R >= 16 else max(nq or 0, nr or 0), int(self.args.batch_per_gpu)
-        swd = SlicedWasserstein(ops, R, n, seed=val["seed"]) if R >= 16 else None
-        pairs = val.get("msssim_pairs") if R >= 16 else None
-        ms = None
-        if pairs:       # the first 2 * pairs images of each set, as they pass by
-            from .metrics import MultiScaleSSIM
-            ms = {w: MultiScaleSSIM(ops, R, pairs) for w in ("real", "fake")}
-        nn = nn_q = None
-        if nq:          # the first nq images of each set, as rows at the comparison resolution
-            from .metrics import NearestNeighbours
-            k, rc = self._nn_settings()
-            nn = NearestNeighbours(ops, R, k, min(rc, R))
-            nn_q = {w: [] for w in ("real", "fake")}
-            nn_fakes = []       # the first 8 generated images, for the figure
-        rec_t = {w: [] for w in ("real", "fake")} if nr else None   # the first nr images of each set
-
-        def feed(which, x):
-            if rec_t is not None:
-                have = sum(t.shape[0] for t in rec_t[which])
-                if have < nr:
-                    rec_t[which].append(x[:nr - have].detach().float().cpu())
-            if swd is not None:
-                swd.feed(which, x)
-            if ms is not None and ms[which].fed < 2 * pairs:
-                ms[which].feed(x[:2 * pairs - ms[which].fed])
-            if nn is not None:
-                have = sum(d.shape[0] for d, _ in nn_q[which])
-                if have < nq:
-                    nn_q[which].append(nn.descriptors(x[:nq - have]))
-                    if which == "fake" and have < 8:
-                        nn_fakes.append(x[:8 - have].detach().float().cpu())
-
-        for x in self._valid_reals(R, n, B):
-            feed("real", x)
-        g = torch.Generator().manual_seed(val["seed"])
-        for i in range(0, n, B):     # always whole batches: one sampling engine shape
-            z = torch.randn(B, self.args.latent_dim, generator=g).to(self.device)
-            feed("fake", self.sample(z, ema=self.G_ema is not None)[:n - i])
-        d = f"{self.args.save_root}/{self.args.run_id}"
-        os.makedirs(d, exist_ok=True)
-        out = {}
-        if swd is not None:
-            out = swd.result()
-            levels = [out[k] for k in swd.sizes]
-            if master:
-                print(f"step {step}: SWD x1e3 " + " ".join(f"{k}:{out[k]:.4f}" for k in swd.sizes) +
-                      f" avg:{out['avg']:.4f}")
-            with open(f"{d}/swd.csv", "a") as f:
-                f.write(",".join([str(step), str(self.scale_index)] +
-                                 [repr(v) for v in levels + [out["avg"]]]) + "\n")
-        if ms is not None:
-            out["msssim"], out["msssim_real"] = ms["fake"].result(), ms["real"].result()
-            if master:
-                print(f"step {step}: MS-SSIM {out['msssim']:.4f} (reals {out['msssim_real']:.4f})")
-            with open(f"{d}/msssim.csv", "a") as f:
-                f.write(",".join([str(step), str(self.scale_index), repr(out["msssim"]),
-                                  repr(out["msssim_real"])]) + "\n")
-        if nn is not None:
-            out.update(self._nn_validation(nn, nn_q, torch.cat(nn_fakes), step, d, master))
-        if rec_t is not None:
-            out.update(self._recover_validation({w: torch.cat(t) for w, t in rec_t.items()}, step, d))
-        return out
+        return self._validation.run(step)
 
     def recover(self, images, fade=True, **kw):
         """Latent recovery (pggan_amd.recover.recover_latents): (z, loss, mse0, reconstructions)
@@ -585,110 +380,7 @@ class ProgressiveGAN:
         are the generator's own output already).  kw: recover_latents'
         (steps, lr, levels, seed, z0, betas, batch).  Runs on buffers of its own: the training
         engine, the RNG offsets and the optimiser state are not touched."""
-        from .recover import recover_latents
-        self.flush()
-        net = self.G
-        if self.G_ema is not None:
-            net = self.G_ema
-            net.alpha = self.G.alpha
-        R = 4 * 2 ** self.scale_index
-        x = images.to(self.device)
-        if x.dtype == torch.uint8 and x.dim() == 4 and x.shape[3] == 3:
-            x = x.permute(0, 3, 1, 2).float() / 127.5 - 1
-        if x.dim() != 4 or tuple(x.shape[1:]) != (3, R, R):
-            raise ValueError(f"recover: images must be fp32 [N, 3, {R}, {R}] or uint8 [N, {R}, {R}, 3], "
-                             f"got {images.dtype} {tuple(images.shape)}")
-        x = x.float().contiguous()
-        alpha = float(net.alpha)
-        if fade and self.scale_index >= 1 and alpha != 1.0:
-            faded = torch.empty_like(x)
-            self._nn_ops().img_fade(x, alpha, faded)
-            x = faded
-        return recover_latents(net, x, **kw)
-
-    def _recover_validation(self, sets, step, d):
-        """The latent-recovery part of validation(): `sets` {"real" / "fake": fp32 [N, 3, R, R]
-        on the host}, the held-out reals and the generator's own samples; the training set's
-        first N images are fetched here, un-augmented.  Returns {"rec_train", "rec_real",
-        "rec_fake"}: the median over each set of sqrt(mse0) * 127.5, the RMS reconstruction error
-        on the 0..255 scale nn.csv uses.  rec_fake calibrates the optimiser (the generator can
-        produce its own samples: if this is not near zero the search fails, not the
-        generator); rec_train far below rec_real is memorisation.  Appends
-        step,scale,steps,levels,rec_train,rec_real,rec_fake to recover.csv and writes
-        recover/e{step}.jpg: the first 8 training targets, their reconstructions, the first 8
-        held-out targets, their reconstructions."""
-        from PIL import Image
-        from .recover import default_levels
-        kw = self._recover_settings()
-        # the starting latents come from seed + 2: not the draws (seed) behind the generated set
-        n = sets["real"].shape[0]
-        R = 4 * 2 ** self.scale_index
-        if kw["levels"] is None:
-            kw["levels"] = default_levels(R)
-        kw["levels"] = min(kw["levels"], int(math.log2(R)) + 1)
-        if self.train_dataset is None:
-            if self.synthetic is None:
-                raise RuntimeError("latent recovery: no training images (set_dataset first)")
-            sets["train"] = self.synthetic[[j % self.synthetic.shape[0] for j in range(n)]].float()
-        else:
-            idx = [j % len(self.train_dataset) for j in range(n)]
-            sets["train"] = self._stage_loader().raw_u8(idx)
-        out, shown = {}, {}
-        for w in ("train", "real", "fake"):
-            _, _, mse0, img = self.recover(sets[w], fade=w != "fake",
-                                           batch=int(self.args.batch_per_gpu),
-                                           seed=self._val["seed"] + 2, **kw)
-            out[f"rec_{w}"] = float(np.median(np.sqrt(mse0.double().cpu().numpy()) * 127.5))
-            shown[w] = img[:8].float().cpu()
-        print(f"step {step}: latent recovery, {kw['steps']} steps, {kw['levels']} levels, RMS of 255: "
-              f"train {out['rec_train']:.3f} held-out {out['rec_real']:.3f} "
-              f"generated {out['rec_fake']:.3f}")
-        with open(f"{d}/recover.csv", "a") as f:
-            f.write(",".join([str(step), str(self.scale_index), str(kw["steps"]), str(kw["levels"]),
-                              repr(out["rec_train"]), repr(out["rec_real"]),
-                              repr(out["rec_fake"])]) + "\n")
-        tr = sets["train"][:8]
-        if tr.dtype == torch.uint8:
-            tr = tr.permute(0, 3, 1, 2).float() / 127.5 - 1
-        rows = [tr.float().cpu(), shown["train"], sets["real"][:8], shown["real"]]
-        grid = make_grid_image(rows).permute(1, 2, 0).numpy().astype(np.float64) * 255
-        os.makedirs(f"{d}/recover", exist_ok=True)
-        Image.fromarray(np.clip(np.rint(grid), 0, 255).astype(np.uint8)).save(
-            f"{d}/recover/e{step}.jpg")
-        return out
-
-    def _nn_validation(self, nn, queries, fakes, step, d, master):
-        """The nearest-neighbour part of validation(): `queries` {"real" / "fake": [(rows,
-        sums), ..]} against the stage's training images.  Returns {"nn", "nn_real"}: the median
-        over the queries of the RMS pixel distance (0..255 scale) to the nearest training
-        image, and "nn_min", the generated images' smallest: a generator that copies training
-        images shows as nn, nn_min far below nn_real, the held-out reals' own distance.
-        Appends step,scale,Rc,nn,nn_min,nn_real to nn.csv and writes nn/e{step}.jpg: the first
-        8 generated images in the top row, under each its k nearest training images."""
-        from PIL import Image
-        desc, sq = self._nn_database(nn)
-        near, res = {}, {}
-        for w in ("fake", "real"):
-            nn.set_query_descriptors(torch.cat([q for q, _ in queries[w]]),
-                                     torch.cat([s for _, s in queries[w]]))
-            nn.feed_descriptors(desc, sq, 0)
-            near[w] = nn.rms()[:, 0].cpu().numpy()
-            res[w] = nn.result()[0].cpu()
-        out = {"nn": float(np.median(near["fake"])), "nn_real": float(np.median(near["real"])),
-               "nn_min": float(near["fake"].min())}
-        if master:
-            print(f"step {step}: nearest training image at {nn.Rc}x{nn.Rc}, RMS of 255: median "
-                  f"{out['nn']:.3f} min {out['nn_min']:.3f} (reals {out['nn_real']:.3f})")
-        with open(f"{d}/nn.csv", "a") as f:
-            f.write(",".join([str(step), str(self.scale_index), str(nn.Rc), repr(out["nn"]),
-                              repr(out["nn_min"]), repr(out["nn_real"])]) + "\n")
-        idx = res["fake"][:fakes.shape[0]]
-        fakes = fakes[:idx.shape[0]]        # fewer than 8 queries: those
-        rows = [fakes] + [self._nn_images(idx[:, j].tolist()) for j in range(nn.k)]
-        grid = make_grid_image(rows).permute(1, 2, 0).numpy().astype(np.float64) * 255
-        os.makedirs(f"{d}/nn", exist_ok=True)
-        Image.fromarray(np.clip(np.rint(grid), 0, 255).astype(np.uint8)).save(f"{d}/nn/e{step}.jpg")
-        return out
+        return self._validation.recover(images, fade, **kw)
 
     # ------------------------------------------------------------------ step
     def _engine(self, B):
@@ -932,7 +624,7 @@ class ProgressiveGAN:
     def reset_solver(self):
         """pggan/model.py:131-139."""
         self.flush()
-        self._nn_db = None       # the nearest-neighbour database of the stage that ends
+        self._validation.stage_changed()
         self.set_dataset()
         self.set_data_iterator()
         self.set_optimizers()
@@ -1056,11 +748,7 @@ class ProgressiveGAN:
     def save_image(self, images, step):
         """lib/utils.py:86-91: make_grid_image(images) * 255 written to
         {save_root}/{run_id}/imgs/e{step}.jpg (cv2.imwrite saturates and rounds to uint8)."""
-        from PIL import Image
-        grid = make_grid_image(images).permute(1, 2, 0).numpy().astype(np.float64) * 255
-        d = f"{self.args.save_root}/{self.args.run_id}/imgs"
-        os.makedirs(d, exist_ok=True)
-        Image.fromarray(np.clip(np.rint(grid), 0, 255).astype(np.uint8)).save(f"{d}/e{step}.jpg")
+        save_grid_jpg(images, f"{self.args.save_root}/{self.args.run_id}/imgs", step)
 
 
 def sampler_order(n, rank, world, distributed=None):
@@ -1095,6 +783,14 @@ def make_grid_image(list_of_tensors):
         t = t[:8].detach().float().cpu()
         rows.append(_make_grid(t, nrow=t.shape[0]) * 0.5 + 0.5)
     return torch.cat(rows, dim=1)
+
+
+def save_grid_jpg(list_of_tensors, d, step):
+    """make_grid_image * 255 as {d}/e{step}.jpg, saturated and rounded to uint8."""
+    from PIL import Image
+    grid = make_grid_image(list_of_tensors).permute(1, 2, 0).numpy().astype(np.float64) * 255
+    os.makedirs(d, exist_ok=True)
+    Image.fromarray(np.clip(np.rint(grid), 0, 255).astype(np.uint8)).save(f"{d}/e{step}.jpg")
 
 
 def _make_grid(t, nrow, padding=2, pad_value=0.0):

@@ -230,7 +230,7 @@ def test_validation_with_msssim_pairs(tmp_path, cpu_model):
     fakes = torch.cat([on.sample(torch.randn(4, on.args.latent_dim, generator=g), ema=False)
                        for _ in range(2)])
     ref = M.msssim_reference(fakes[:6].numpy())
-    reals = torch.cat(list(on._valid_reals(16, 8, 4)))
+    reals = torch.cat(list(on._validation.reals(16, 8, 4)))
     ref_real = M.msssim_reference(reals[:6].numpy())
     print(f"msssim {out['msssim']} ref {ref}; reals {out['msssim_real']} ref {ref_real}")
     assert isinstance(out["msssim"], float) and isinstance(out["msssim_real"], float)

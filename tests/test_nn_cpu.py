@@ -301,7 +301,7 @@ def test_validation_with_nn_queries(tmp_path, cpu_model):
     g = torch.Generator().manual_seed(0)
     fakes = torch.cat([on.sample(torch.randn(4, on.args.latent_dim, generator=g), ema=False)
                        for _ in range(2)])[:5]
-    reals = torch.cat(list(on._valid_reals(16, 8, 4)))[:5]
+    reals = torch.cat(list(on._validation.reals(16, 8, 4)))[:5]
     rf, rr = nn_figures(on, fakes, 16, 3)[0], nn_figures(on, reals, 16, 3)[0]
     assert out["nn"] == float(np.median(rf[:, 0])) and out["nn_min"] == float(rf[:, 0].min())
     assert out["nn_real"] == float(np.median(rr[:, 0]))
@@ -327,9 +327,9 @@ def test_validation_with_nn_queries(tmp_path, cpu_model):
     assert idx[:, 0].tolist() == [0, 1, 2, 3] and d2[:, 0].tolist() == [0, 0, 0, 0]
     assert_unchanged(on, before)
     # the database is kept for the stage and dropped with it
-    assert on._nn_db[0] == (2, 16) and tuple(on._nn_db[1].shape) == (4, 768)
+    assert on._validation.nn_db[0] == (2, 16) and tuple(on._validation.nn_db[1].shape) == (4, 768)
     on.reset_solver()
-    assert on._nn_db is None
+    assert on._validation.nn_db is None
     # training goes on exactly as without it
     off.reset_solver()
     for m in (on, off):

@@ -288,7 +288,7 @@ def test_held_out_split(tmp_path, cpu_model):
     assert len(m.valid_paths) == 3 and not set(m.valid_paths) & set(m.train_dataset.paths)
     assert sorted(m.valid_paths + m.train_dataset.paths) == sorted(paths)
     # the 3 held-out images, decoded at 16x16 and wrapped around to 8 reals
-    reals = torch.cat(list(m._valid_reals(16, 8, 4)))
+    reals = torch.cat(list(m._validation.reals(16, 8, 4)))
     assert reals.shape == (8, 3, 16, 16) and torch.equal(reals[0], reals[3])
     u8 = torch.round(reals * 127.5 + 127.5)
     assert float((u8 - (reals * 127.5 + 127.5)).abs().max()) < 1e-4 and 0 <= u8.min() and u8.max() <= 255
@@ -296,4 +296,4 @@ def test_held_out_split(tmp_path, cpu_model):
     assert set(out) == {16, "avg"} and out[16] > 0
     # valid_dataset_root takes precedence
     m.args.valid_dataset_root = str(root)
-    assert len(torch.cat(list(m._valid_reals(16, 10, 4))).unique(dim=0)) == 10
+    assert len(torch.cat(list(m._validation.reals(16, 10, 4))).unique(dim=0)) == 10
