@@ -541,6 +541,29 @@ int pg_latent_step(int B, int Lz, float* z, const float* gzn, float* m, float* v
                    double beta1, double beta2, double eps, int step, const float* loss,
                    float* best_loss, float* best_z, float* gz_out, void* stream);
 
+/* ---- radial power spectrum of images (the network-free check of a generator's high
+ * frequencies; DESIGN.md "Validation: power spectrum").  All fp32; x NCHW [B][3][R][R], R a
+ * power of two, 8 <= R <= 1024, 1 <= B <= 65535.  Per image:
+ *   1. `quantize` != 0: q = rint(clip(127.5 x + 127.5, 0, 255)), ties to even, as
+ *      pg_swd_pyr_down reads an image; otherwise q = x, taken on the 0..255 scale;
+ *   2. luma, shifted: y = 0.299 (q_r - 127.5) + 0.587 (q_g - 127.5) + 0.114 (q_b - 127.5);
+ *   3. F(u, v) = sum_{r,c} y(r, c) exp(-2 pi i (u r + v c) / R): unnormalised, no window; the
+ *      signed frequencies u, v lie in [-R/2, R/2);
+ *   4. (u, v) belongs to radius bin k, the one integer with k^2 - k < u^2 + v^2 <= k^2 + k
+ *      ((0, 0): bin 0) -- round(sqrt(u^2 + v^2)) in integers; bins k > R/2 are dropped;
+ *   5. prof[b][k] = sum over the full plane of |F(u, v)|^2 in bin k, k = 0 .. R/2.
+ * A real 2-D FFT in LDS (twiddles from sincospif of exact arguments); the complex spectrum is
+ * never written out.  R <= 64: one launch, one workgroup per image.  Larger R: a row pass
+ * that stores the half spectrum transposed in `ws`, a column pass that writes fp32 bin sums
+ * per workgroup to `ws`, and a launch that adds an image's partials in double in a fixed order.
+ * No float atomics: an image's profile is bitwise repeatable and does not depend on B or on
+ * its place in the batch.  ws: pg_spectrum_workspace_bytes(B, R) of device memory (0 for
+ * arguments out of range; at most about 33 MB: images are taken in chunks).  x, prof and ws
+ * non-null and 16-byte aligned; every failed check is PG_ERR_ARG before any launch. */
+size_t pg_spectrum_workspace_bytes(int B, int R);
+int pg_spectrum_profile(int B, int R, const float* x, int quantize, float* prof /* [B][R/2+1] */,
+                        void* ws, size_t ws_bytes, void* stream);
+
 /* ---- stream ordering between the engine's streams (weight gradients on a side stream).
  * torch's cross-stream events record with a system-scope release: every record writes back and
  * invalidates the L2 of all XCDs and the next kernel on that stream starts ~6.5 us late.  The

@@ -172,6 +172,8 @@ _SIGS = {
     "pg_recon_loss": ([_I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP], _I),
     "pg_latent_step": ([_I, _I, _VP, _VP, _VP, _VP, _D, _D, _D, _D, _I, _VP, _VP, _VP, _VP, _VP],
                        _I),
+    "pg_spectrum_workspace_bytes": ([_I, _I], _SZ),
+    "pg_spectrum_profile": ([_I, _I, _VP, _I, _VP, _VP, _SZ, _VP], _I),
     "pg_step_plan_create": ([_I, _I, ctypes.POINTER(ctypes.c_int), _I, _I,
                              ctypes.POINTER(ctypes.c_void_p)], _I),
     "pg_step_plan_workspace_size": ([_VP], _SZ),
@@ -981,6 +983,29 @@ class HipOps:
         self._chk(self.lib.pg_latent_step(B, Lz, _p(z), _p(gzn), _p(m), _p(v), lr, beta1, beta2, eps,
                                           int(step), _p(loss), _p(best_loss), _p(best_z),
                                           _p(gz_out), self._s()), "latent_step")
+
+    # -- radial power spectrum (pggan_amd/metrics.py, csrc/spectrum.hip) ----
+    def spectrum_profile(self, x, quantize, out):
+        """out fp32 [B, R/2+1]: per image of x (fp32 [B,3,R,R], R a power of two in [8, 1024])
+        the power |DFT2(luma)|^2 summed over the integer radius bins 0 .. R/2
+        (pg_spectrum_profile).  The workspace is kept by the op set and grows to the largest
+        (B, R) seen."""
+        self._cuda_named("spectrum_profile", x, out)
+        if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous() or \
+                x.shape[1] != 3 or x.shape[2] != x.shape[3]:
+            raise RuntimeError("pggan_amd: spectrum_profile takes a contiguous fp32 [B,3,R,R] batch, "
+                               f"got {x.dtype} {tuple(x.shape)}")
+        B, R = x.shape[0], x.shape[2]
+        if out.dtype != torch.float32 or not out.is_contiguous() or \
+                tuple(out.shape) != (B, R // 2 + 1):
+            raise RuntimeError(f"pggan_amd: spectrum_profile writes fp32 [{B}, {R // 2 + 1}] "
+                               f"profiles, got {out.dtype} {tuple(out.shape)}")
+        need = int(self.lib.pg_spectrum_workspace_bytes(B, R))      # 0: the call below says why
+        ws = getattr(self, "_spws", None)
+        if ws is None or ws.numel() * 4 < need or ws.device != x.device:
+            ws = self._spws = torch.empty(max(need // 4, 4), dtype=torch.float32, device=x.device)
+        self._chk(self.lib.pg_spectrum_profile(B, R, _p(x), 1 if quantize else 0, _p(out), _p(ws),
+                                               ws.numel() * 4, self._s()), "spectrum_profile")
 
     def cast(self, x, y):
         self._cuda(x, y)

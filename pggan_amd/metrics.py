@@ -18,8 +18,14 @@ one set (MultiScaleSSIM below; csrc/msssim.hip through the op set's msssim_* met
 
 And its nearest-neighbour figure: the training images closest to given images in pixel space
 (NearestNeighbours below; csrc/nn.hip through the op set's nn_* methods).
+
+And, beyond the paper, the radial power spectrum of a set of images, the network-free check of
+a generator's high frequencies (PowerSpectrum below; csrc/spectrum.hip through the op set's
+spectrum_profile).
 """
 from __future__ import annotations
+
+import functools
 
 import numpy as np
 import torch
@@ -346,3 +352,103 @@ class NearestNeighbours:
         idx, d2 = (t.cpu() for t in self.result())
         r = (d2.double() / self.D).sqrt()
         return torch.where(idx < 0, torch.full_like(r, float("inf")), r)
+
+
+# ---------------------------------------------------------------------------- power spectrum
+SPECTRUM_FLOOR = 1e-12       # a bin mean below this counts as this in the dB ratio
+
+
+def spectrum_bin_index(r2):
+    """The radius bin of the squared radii r2 (non-negative integers): the one k with
+    k^2 - k < r2 <= k^2 + k (0 for r2 = 0): round(sqrt(r2)), decided in integers (the float
+    root only proposes floor(sqrt(r2)), which is then corrected)."""
+    r2 = np.asarray(r2, dtype=np.int64)
+    k = np.sqrt(r2.astype(np.float64)).astype(np.int64)
+    k = np.where(k * k > r2, k - 1, k)
+    k = np.where((k + 1) * (k + 1) <= r2, k + 1, k)
+    return np.where(r2 > k * k + k, k + 1, k)
+
+
+def spectrum_bins(R):
+    """int64 [R, R]: the bin of every point of the DFT plane in numpy.fft order (index i is
+    the signed frequency i for i < R/2, i - R from R/2 on)."""
+    f = np.arange(R, dtype=np.int64)
+    f = np.where(f < R // 2, f, f - R)
+    return spectrum_bin_index(f[:, None] ** 2 + f[None, :] ** 2)
+
+
+@functools.lru_cache(maxsize=None)
+def _spectrum_bin_counts(R):
+    return np.bincount(spectrum_bins(R).ravel())[:R // 2 + 1].astype(np.int64)
+
+
+def spectrum_bin_counts(R):
+    """int64 [R/2 + 1]: the number of points of the R x R plane in each bin 0 .. R/2 (a
+    function of R alone: computed once per R)."""
+    return _spectrum_bin_counts(int(R)).copy()
+
+
+def spectrum_db(S_real, S_fake):
+    """10 log10(S_fake / S_real) per bin of two profiles [K + 1], either side floored at 1e-12."""
+    a, b = (np.maximum(np.asarray(s, np.float64), SPECTRUM_FLOOR) for s in (S_real, S_fake))
+    if a.shape != b.shape or a.ndim != 1 or a.size < 5:
+        raise ValueError("spectrum_db: two profiles of one length >= 5")
+    return 10.0 * np.log10(b / a)
+
+
+def spectrum_compare(S_real, S_fake):
+    """(dB [K], spec_dist, spec_hf) of two profiles [K + 1]: dB[k - 1] = 10 log10(S_fake[k] /
+    S_real[k]) for k = 1 .. K (bin 0, the brightness, is left out; either side floored at
+    1e-12), spec_dist the mean of |dB|, spec_hf the signed mean of dB over the top quarter
+    k = 3K/4 + 1 .. K: positive is too much fine detail or noise, negative too little."""
+    db = spectrum_db(S_real, S_fake)[1:]
+    K = db.size
+    return db, float(np.abs(db).mean()), float(db[3 * K // 4:].mean())
+
+
+class PowerSpectrum:
+    """The azimuthally averaged power spectrum of a set of images (Durall et al. 2020, "Watch
+    your Up-Convolution"; DESIGN.md "Validation: power spectrum"): per image |DFT2(luma)|^2 of
+    the 8-bit image summed over integer radius bins 0 .. K = R/2 in the library
+    (csrc/spectrum.hip through the op set's spectrum_profile), averaged here over the images
+    and the bin populations in float64.
+
+        m = PowerSpectrum(ops, 256)
+        for batch in fakes: m.feed(batch)       # fp32 [B, 3, 256, 256] in [-1, 1]
+        m.profile()                             # float64 [129]; spectrum_compare(real, fake)
+
+    quantize=False takes the images as they are, on the 0..255 scale.  The per-image profiles
+    stay on the device, (K + 1) floats each."""
+
+    def __init__(self, ops, resolution, quantize=True):
+        R = int(resolution)
+        if R < 8 or R > 1024 or R & (R - 1):
+            raise ValueError(f"PowerSpectrum: resolution must be a power of two in [8, 1024], got {R}")
+        self.ops, self.R, self.K, self.quantize = ops, R, R // 2, bool(quantize)
+        self.counts = spectrum_bin_counts(R)
+        self.count = 0               # images fed
+        self._prof = []              # fp32 [B, K + 1] per feed
+
+    def feed(self, images):
+        if images.dim() != 4 or tuple(images.shape[1:]) != (3, self.R, self.R):
+            raise ValueError(f"PowerSpectrum.feed: expected [B, 3, {self.R}, {self.R}], got "
+                             f"{tuple(images.shape)}")
+        B = images.shape[0]
+        if B == 0:
+            return
+        x = images.detach().to(torch.float32).contiguous()
+        out = torch.empty(B, self.K + 1, dtype=torch.float32, device=x.device)
+        self.ops.spectrum_profile(x, self.quantize, out)
+        self._prof.append(out)
+        self.count += B
+
+    def per_image(self):
+        """The profiles as the library wrote them, fp32 [count, K + 1], in feed order."""
+        if not self._prof:
+            raise RuntimeError("PowerSpectrum: no image fed")
+        return torch.cat(self._prof)
+
+    def profile(self):
+        """S[k]: the mean over the images of prof[k] / count[k], float64 numpy [K + 1]."""
+        total = self.per_image().double().sum(dim=0).cpu().numpy()
+        return total / self.count / self.counts

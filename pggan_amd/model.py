@@ -21,7 +21,8 @@ Differences (deliberate):
     Wasserstein distance on the held-out 30 % of the images (pggan_amd.metrics); config
     `msssim_pairs` (blank: off) adds the paper's MS-SSIM between pairs of generated images,
     `nn_queries` (blank: off) the distance to the nearest training images, `recover_images`
-    (blank: off) latent recovery of training, held-out and generated images (also `recover()`).
+    (blank: off) latent recovery of training, held-out and generated images (also `recover()`),
+    `spectrum_images` (blank: off) the radial power spectrum of generated against real images.
 """
 from __future__ import annotations
 
@@ -368,7 +369,10 @@ class ProgressiveGAN:
         With `recover_images` the first recover_images training images, held-out reals and
         generated images are recovered from the generator (validation.RecoverPart: "rec_train",
         "rec_real", "rec_fake", recover.csv, recover/e{step}.jpg), on the master, at every
-        stage."""
+        stage.
+        With `spectrum_images` the radial power spectra of the first spectrum_images images of
+        each set are compared in dB (validation.SpectrumPart: "spec_dist", "spec_hf",
+        spectrum.csv, spectrum/e{step}.csv), from 16 x 16 on."""
         return self._validation.run(step)
 
     def recover(self, images, fade=True, **kw):

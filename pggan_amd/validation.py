@@ -1,7 +1,7 @@
 """ProgressiveGAN's validation (config `use_validation`): one `Validation` per model, which
 streams reals and generated images once through the parts that are configured -- the paper's
-sliced Wasserstein distance, its MS-SSIM, the nearest training images and latent recovery --
-and owns what they share: the settings, one fp32 op set, the stage's nearest-neighbour
+sliced Wasserstein distance, its MS-SSIM, the nearest training images, latent recovery and the
+radial power spectrum -- and owns what they share: the settings, one fp32 op set, the stage's nearest-neighbour
 database.  The metrics themselves are pggan_amd.metrics and pggan_amd.recover.
 
 A part is a plain class with
@@ -21,7 +21,8 @@ import torch
 
 from .config import cfg_get
 from .data import image_paths, load_u8
-from .metrics import NN_MAX_K, SETS, MultiScaleSSIM, NearestNeighbours, SlicedWasserstein
+from .metrics import (NN_MAX_K, SETS, MultiScaleSSIM, NearestNeighbours, PowerSpectrum,
+                      SlicedWasserstein, spectrum_compare, spectrum_db)
 from .recover import default_levels, recover_latents
 
 
@@ -107,6 +108,7 @@ class Settings:
         self.nn = nn_settings(args) if self.nn_queries else None
         self.recover_images = leading_count(args, "recover_images", "targets", self.images)
         self.recover = recover_settings(args) if self.recover_images else None
+        self.spectrum_images = leading_count(args, "spectrum_images", "images", self.images)
 
 
 # ---------------------------------------------------------------------- the parts
@@ -276,7 +278,48 @@ class RecoverPart:
         return out
 
 
-PARTS = (SwdPart, MsssimPart, NnPart, RecoverPart)
+class SpectrumPart:
+    """The radial power spectra of the first spectrum_images images of each set (luma of the
+    8-bit image, |DFT2|^2 averaged over integer radius bins 0 .. K = R/2), compared bin by bin
+    in dB, generated over real.  "spec_dist": the mean of |dB| over the bins 1 .. K;
+    "spec_hf": the signed mean of dB over the top quarter of the bins -- positive: the
+    generator has too much fine detail or noise, negative: too little (during the fade-in of a
+    new block this quarter fills as alpha rises).  spectrum.csv: step,scale,spec_dist,spec_hf;
+    spectrum/e{step}.csv, on the master: k,S_real,S_fake,dB per bin, bin 0 included."""
+    name, min_res = "the power spectrum", 16
+
+    @staticmethod
+    def wants(s, master):
+        return s.spectrum_images
+
+    def __init__(self, val, R, n):
+        self.n, self.val, self.first = n, val, Leading(n)
+        self.ps = {w: PowerSpectrum(val.ops, R) for w in SETS}
+
+    def feed(self, which, x):
+        x = self.first.cut(which, x)
+        if len(x):
+            self.ps[which].feed(x)
+
+    def finish(self, step, d, master):
+        S = {w: self.ps[w].profile() for w in SETS}
+        _, dist, hf = spectrum_compare(S["real"], S["fake"])
+        out = {"spec_dist": dist, "spec_hf": hf}
+        if master:
+            print(f"step {step}: power spectrum, dB fake/real: mean |.| {dist:.3f}, "
+                  f"top quarter {hf:+.3f}")
+        append_csv(f"{d}/spectrum.csv", step, self.val.model.scale_index, dist, hf)
+        if master:
+            os.makedirs(f"{d}/spectrum", exist_ok=True)
+            path = f"{d}/spectrum/e{step}.csv"
+            open(path, "w").close()         # a step validated again replaces its table
+            db = spectrum_db(S["real"], S["fake"])
+            for k in range(len(db)):
+                append_csv(path, k, float(S["real"][k]), float(S["fake"][k]), float(db[k]))
+        return out
+
+
+PARTS = (SwdPart, MsssimPart, NnPart, RecoverPart, SpectrumPart)
 
 
 # ---------------------------------------------------------------------- the model's side

@@ -136,7 +136,60 @@ def msssim(IW, HP, RP, IH=42, NJ=8):
     return {"passes": passes, "h_read": round(rd / nr, 3), "h_write": round(wr / nw, 3)}
 
 
+W64_GROUPS = [list(range(g, g + 16)) for g in range(0, 64, 16)]     # ds_write_b64
+
+
+def spectrum(R, pad=True, odd_pitch=True):
+    """csrc/spectrum.hip: lines of R complex (8-B) elements, element p at p + (p >> 5), lines
+    R + R/32 + 1 apart (pad / odd_pitch False: the plain layout, for comparison).  Mean LDS
+    cycles per lane group (1.0 = conflict free) of the 8-B reads (64 banks) and writes (32
+    banks) of every pass of the FFT -- "q": a radix-4 item's four elements at quarter-span q,
+    "r2": the last radix-2 pass of an odd log2 R -- and of the bit-reversed reads of the
+    transposing store of the row pass ("untangle": item = (frequency v, line i), i fastest)."""
+    logR = R.bit_length() - 1
+    at = (lambda p: p + (p >> 5)) if pad else (lambda p: p)
+    pitch = R + ((R >> 5) if pad else 0) + (1 if odd_pitch else 0)
+    NL = min(4096 // R, 8)
+    brev = lambda f: int(format(f, f"0{logR}b")[::-1], 2)
+
+    def mean(items, elems):
+        """items: a list of per-item element lists; one access per element slot."""
+        rd = wr = nr = nw = 0
+        for w0 in range(0, len(items), 64):
+            wave = items[w0:w0 + 64] + [None] * (w0 + 64 - len(items))
+            for e in range(elems):
+                a = [None if it is None else it[e] * 8 for it in wave]
+                c, n = masked_cycles(a, B64_GROUPS, 64, 2)
+                rd, nr = rd + c, nr + n
+                c, n = masked_cycles(a, W64_GROUPS, 32, 2)
+                wr, nw = wr + c, nw + n
+        return round(rd / nr, 2), round(wr / nw, 2)
+
+    res = {}
+    lg = logR
+    while lg >= 2:
+        q, items = 1 << (lg - 2), []
+        for it in range(NL << (logR - 2)):
+            l, t = it >> (logR - 2), it & ((R >> 2) - 1)
+            p0 = ((t >> (lg - 2)) << lg) + (t & (q - 1))
+            items.append([l * pitch + at(p0 + m * q) for m in range(4)])
+        res[f"q={q}"] = mean(items, 4)
+        lg -= 2
+    if lg == 1:
+        items = [[(it >> (logR - 1)) * pitch + at(((it & ((R >> 1) - 1)) << 1) + m) for m in range(2)]
+                 for it in range(NL << (logR - 1))]
+        res["r2"] = mean(items, 2)
+    items = [[(it % NL) * pitch + at(brev(it // NL)), (it % NL) * pitch + at(brev((R - it // NL) & (R - 1)))]
+             for it in range((R // 2 + 1) * NL)]
+    res["untangle"] = mean(items, 2)[0]
+    return res
+
+
 if __name__ == "__main__":
+    print("spectrum (per pass: mean read, write cycles per lane group; padded / plain layout):")
+    for R in (128, 256, 512, 1024):
+        print(f"  R {R}:", spectrum(R))
+        print(f"  R {R} plain:", spectrum(R, pad=False, odd_pitch=False))
     print("msssim (s_in pitch IW, s_h pitch HP, item rows per column group RP):")
     for RP in (42, 48, 64):
         for IW in (44, 48):
