@@ -564,6 +564,44 @@ size_t pg_spectrum_workspace_bytes(int B, int R);
 int pg_spectrum_profile(int B, int R, const float* x, int quantize, float* prof /* [B][R/2+1] */,
                         void* ws, size_t ws_bytes, void* stream);
 
+/* ---- training health: per-tensor statistics of a net's flat fp32 buffers and the every-step
+ * non-finite probe (DESIGN.md "Training health"; pggan_amd/health.py).
+ * A segment table is a DEVICE array of nseg int64 pairs {offset, count} into one flat fp32
+ * buffer of n floats: offsets are multiples of 16 floats, count is the tensor's true element
+ * count, segments are disjoint and ascending and end at or before n.  The floats between
+ * offset + count and the next offset are padding and are never read (whole quads are 16-byte
+ * loads, a tensor's last 1 .. 3 elements scalar loads; every byte is read once).
+ *
+ * pg_tensor_stats: p, g, m, v are flat fp32 device buffers of n floats with that layout, each
+ * nullable.  out [nseg][PG_TS_COLS] doubles (device) is WRITTEN, per segment:
+ *   0-2  sumsq_p, sumsq_g, sumsq_u    sums of squares over the finite elements
+ *   3-5  maxabs_p, maxabs_g, maxabs_u largest magnitudes over the finite elements
+ *   6-9  bad_p, bad_g, bad_m, bad_v   elements that are +-Inf or NaN
+ * u = step_size m / (sqrt(v) / bc2_sqrt + eps), the magnitude of the update pg_adam applies from
+ * these moments; {step_size, bc2_sqrt} is the pair pg_adam_table holds for that update.  u is
+ * evaluated in double from the fp32 m, v and scalars, each operation rounded on its own, and
+ * taken only where both m and v are finite (v >= 0, as Adam leaves it).  Columns whose buffer
+ * is NULL are 0 (the u columns need both m and v).  All sums are double: the square of an fp32
+ * value is exact there.  The buffer is cut into ranges of pg_tensor_stats_chunk() floats, one
+ * wave each, whatever the segment sizes; a second launch combines the per-(segment, range)
+ * partials in `ws` in a fixed order: no atomics, bitwise repeatable.  ws:
+ * pg_tensor_stats_workspace_bytes(nseg, n) of device memory (0 for arguments out of range).
+ * table, the buffers, out and ws 16-byte aligned; every failed check is PG_ERR_ARG before any
+ * launch.
+ *
+ * pg_nonfinite_watch: one launch over x[0, n) that tests exponent bits only.  For every
+ * segment that holds a non-finite element and whose first_bad [nseg] (device ints, 0 = never)
+ * is still 0, first_bad[segment] = tag (> 0).  Nothing is read back; plain vector stores, and
+ * every writer of a slot within a launch writes the same value. */
+#define PG_TS_COLS 10
+int pg_tensor_stats_chunk(void);
+size_t pg_tensor_stats_workspace_bytes(int nseg, size_t n);
+int pg_tensor_stats(int nseg, const int64_t* table, size_t n, const float* p, const float* g,
+                    const float* m, const float* v, float step_size, float bc2_sqrt, float eps,
+                    double* out /* [nseg][PG_TS_COLS] */, void* ws, size_t ws_bytes, void* stream);
+int pg_nonfinite_watch(int nseg, const int64_t* table, const float* x, size_t n, int tag,
+                       int* first_bad /* [nseg] */, void* stream);
+
 /* ---- stream ordering between the engine's streams (weight gradients on a side stream).
  * torch's cross-stream events record with a system-scope release: every record writes back and
  * invalidates the L2 of all XCDs and the next kernel on that stream starts ~6.5 us late.  The

@@ -174,6 +174,10 @@ _SIGS = {
                        _I),
     "pg_spectrum_workspace_bytes": ([_I, _I], _SZ),
     "pg_spectrum_profile": ([_I, _I, _VP, _I, _VP, _VP, _SZ, _VP], _I),
+    "pg_tensor_stats_chunk": ([], _I),
+    "pg_tensor_stats_workspace_bytes": ([_I, _SZ], _SZ),
+    "pg_tensor_stats": ([_I, _VP, _SZ, _VP, _VP, _VP, _VP, _F, _F, _F, _VP, _VP, _SZ, _VP], _I),
+    "pg_nonfinite_watch": ([_I, _VP, _VP, _SZ, _I, _VP, _VP], _I),
     "pg_step_plan_create": ([_I, _I, ctypes.POINTER(ctypes.c_int), _I, _I,
                              ctypes.POINTER(ctypes.c_void_p)], _I),
     "pg_step_plan_workspace_size": ([_VP], _SZ),
@@ -1006,6 +1010,78 @@ class HipOps:
             ws = self._spws = torch.empty(max(need // 4, 4), dtype=torch.float32, device=x.device)
         self._chk(self.lib.pg_spectrum_profile(B, R, _p(x), 1 if quantize else 0, _p(out), _p(ws),
                                                ws.numel() * 4, self._s()), "spectrum_profile")
+
+    # -- training health (pggan_amd/health.py, csrc/health.hip) ----------------
+    TS_COLS = 10
+
+    @property
+    def tensor_stats_chunk(self):
+        """Floats per wave of tensor_stats (pg_tensor_stats_chunk)."""
+        return int(self.lib.pg_tensor_stats_chunk())
+
+    def adam_pair(self, lr, beta1, beta2, t):
+        """(step_size, bc2_sqrt) of Adam update t >= 1 as pg_adam / pg_adam_table compute them
+        (on the host; the table is cached)."""
+        key = (float(lr), float(beta1), float(beta2))
+        tabs = self.__dict__.setdefault("_adam_host_tabs", {})
+        if key not in tabs:
+            n = int(self.lib.pg_adam_table_len(lr, beta1, beta2))
+            host = (ctypes.c_float * (2 * n))()
+            self._chk(self.lib.pg_adam_table(lr, beta1, beta2, n, host), "adam_table")
+            tabs[key] = (host, n)
+        host, n = tabs[key]
+        k = min(max(int(t), 1), n) - 1
+        return float(host[2 * k]), float(host[2 * k + 1])
+
+    def _seg_table(self, what, table, *bufs):
+        if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 2 or \
+                not table.is_contiguous():
+            raise RuntimeError(f"pggan_amd: {what} takes a contiguous int64 [nseg, 2] segment table, "
+                               f"got {table.dtype} {tuple(table.shape)}")
+        n = None
+        for b in bufs:
+            if b is None:
+                continue
+            if b.dtype != torch.float32 or b.dim() != 1 or not b.is_contiguous():
+                raise RuntimeError(f"pggan_amd: {what} takes flat contiguous fp32 buffers, got "
+                                   f"{b.dtype} {tuple(b.shape)}")
+            if n is not None and b.numel() != n:
+                raise RuntimeError(f"pggan_amd: {what}: buffers of {n} and {b.numel()} floats")
+            n = b.numel()
+        if n is None:
+            raise RuntimeError(f"pggan_amd: {what}: no buffer")
+        return table.shape[0], n
+
+    def tensor_stats(self, table, p, g, m, v, *, step_size, bc2_sqrt, eps, out):
+        """out float64 [nseg, 10]: per segment of `table` (device int64 [nseg, 2] {offset,
+        count}) sumsq / maxabs of p, g and the Adam update u and the non-finite counts of p, g,
+        m, v (pg_tensor_stats; each buffer flat fp32 of one length, or None).  The workspace is
+        kept by the op set and grows to the largest (nseg, n) seen."""
+        self._cuda_named("tensor_stats", table, p, g, m, v, out)
+        nseg, n = self._seg_table("tensor_stats", table, p, g, m, v)
+        if out.dtype != torch.float64 or not out.is_contiguous() or \
+                tuple(out.shape) != (nseg, self.TS_COLS):
+            raise RuntimeError(f"pggan_amd: tensor_stats writes float64 [{nseg}, {self.TS_COLS}], "
+                               f"got {out.dtype} {tuple(out.shape)}")
+        need = int(self.lib.pg_tensor_stats_workspace_bytes(nseg, n))   # 0: the call below says why
+        ws = getattr(self, "_tsws", None)
+        if ws is None or ws.numel() * 8 < need or ws.device != out.device:
+            ws = self._tsws = torch.empty(max(need // 8, 2), dtype=torch.float64, device=out.device)
+        self._chk(self.lib.pg_tensor_stats(nseg, _p(table), n, _p(p), _p(g), _p(m), _p(v),
+                                           step_size, bc2_sqrt, eps, _p(out), _p(ws),
+                                           ws.numel() * 8, self._s()), "tensor_stats")
+
+    def nonfinite_watch(self, table, x, tag, first_bad):
+        """first_bad int32 [nseg]: slots still 0 whose segment of x (flat fp32) holds a
+        non-finite element become `tag` > 0 (pg_nonfinite_watch: one launch, no read-back)."""
+        self._cuda_named("nonfinite_watch", table, x, first_bad)
+        nseg, n = self._seg_table("nonfinite_watch", table, x)
+        if first_bad.dtype != torch.int32 or not first_bad.is_contiguous() or \
+                tuple(first_bad.shape) != (nseg,):
+            raise RuntimeError(f"pggan_amd: nonfinite_watch latches into int32 [{nseg}], got "
+                               f"{first_bad.dtype} {tuple(first_bad.shape)}")
+        self._chk(self.lib.pg_nonfinite_watch(nseg, _p(table), _p(x), n, int(tag), _p(first_bad),
+                                              self._s()), "nonfinite_watch")
 
     def cast(self, x, y):
         self._cuda(x, y)

@@ -23,6 +23,9 @@ Differences (deliberate):
     `nn_queries` (blank: off) the distance to the nearest training images, `recover_images`
     (blank: off) latent recovery of training, held-out and generated images (also `recover()`),
     `spectrum_images` (blank: off) the radial power spectrum of generated against real images.
+  * config `health_cycle` (blank: off) adds health(step): per-tensor norms of parameters,
+    gradients and updates, the first non-finite tensor and step, and a save_checkpoint that
+    refuses to overwrite the last finite checkpoint (pggan_amd.health).
 """
 from __future__ import annotations
 
@@ -39,6 +42,7 @@ from .config import cfg_get
 from .data import BatchLoader, HbmSourceCache, ImageFolderDataset
 from .loss import WGANGPLoss
 from .nets import Discriminator, Generator
+from .health import Health
 from .validation import Validation
 
 
@@ -142,6 +146,7 @@ class ProgressiveGAN:
         self.synthetic = None
         self._exchange = None
         self._validation = Validation(self)
+        self._health = Health(self)     # reads and checks `health_cycle` / `health_on_bad`
 
     # ------------------------------------------------------------------ models
     def initialize_models(self):
@@ -386,6 +391,17 @@ class ProgressiveGAN:
         engine, the RNG offsets and the optimiser state are not touched."""
         return self._validation.recover(images, fade, **kw)
 
+    # ------------------------------------------------------------------ health
+    def health(self, step):
+        """Training health (pggan_amd.health; config `health_cycle`, blank: off -> None).  Call it
+        after train_step on every rank: every call launches the non-finite probe on both nets'
+        first Adam moment, the weight average and the loss scalars (nothing is read back); every
+        `health_cycle`-th step is the full report -- per-tensor RMS of parameters, gradients and
+        Adam updates into {save_root}/{run_id}/health.csv, one printed line, the dict of
+        health.Health.report -- and a non-finite finding raises health.TrainingDiverged
+        (`health_on_bad: warn`: is printed).  Reads buffers between steps only."""
+        return self._health.run(step)
+
     # ------------------------------------------------------------------ step
     def _engine(self, B):
         key = (self.scale_index, B)
@@ -629,6 +645,7 @@ class ProgressiveGAN:
         """pggan/model.py:131-139."""
         self.flush()
         self._validation.stage_changed()
+        self._health.stage_changed()
         self.set_dataset()
         self.set_data_iterator()
         self.set_optimizers()
@@ -695,14 +712,25 @@ class ProgressiveGAN:
                 "next_scale_jump_step": self.next_scale_jump_step}
 
     def save_checkpoint(self, global_step):
-        """pggan/model.py:50-67 + lib/checkpoint.py:22-34 (same paths and keys)."""
+        """pggan/model.py:50-67 + lib/checkpoint.py:22-34 (same paths and keys).
+        With `health_cycle` set the parameters, Adam moments and the weight average are first
+        counted for non-finite values: if there are any, nothing is written (the last finite
+        *_latest.pt stay), the reason is printed and the result is False; True once written."""
         from . import checkpoint
         self.flush()
+        guarded = self._health.settings is not None
+        if guarded:
+            found = self._health.checkpoint_findings()
+            if found:
+                from .health import describe
+                print(f"step {global_step}: checkpoint NOT written: {describe(found)}")
+                return False
         base = self._ckpt_dict(global_step)
         checkpoint.save_checkpoint(self.G, self.opt_G, "G", dict(base))
         checkpoint.save_checkpoint(self.D, self.opt_D, "D", dict(base))
         if self.G_ema is not None:
             checkpoint.save_ema_checkpoint(self.G_ema, self.hyper.ema_decay, dict(base))
+        return True if guarded else None
 
     def load_checkpoint(self):
         """pggan/model.py:70-101: restore schedule scalars, re-add blocks, fresh solver, then

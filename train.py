@@ -25,6 +25,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from pggan_amd.config import Config  # noqa: E402
+from pggan_amd.health import TrainingDiverged, newest_checkpoint  # noqa: E402
 from pggan_amd.model import ProgressiveGAN  # noqa: E402
 
 
@@ -69,9 +70,19 @@ def train(args):
         gen = torch.Generator().manual_seed(1234)
         fixed_z = torch.randn(min(8, args.batch_per_gpu), args.latent_dim,
                               generator=gen).to(model.device)
+    watch_health = bool(args.get("health_cycle"))
     while step < max_step:
         model.check_jump(step)
         images = model.train_step()
+        if watch_health:
+            # every rank, every step (pggan_amd.health): all ranks hold the same parameters
+            # and all-reduced gradients, so all of them stop at the same step
+            try:
+                model.health(step)
+            except TrainingDiverged:
+                if rank == 0:
+                    print(f"training stopped; the newest finite checkpoint: {newest_checkpoint(args)}")
+                raise
         if rank == 0:
             if step % args.loss_cycle == 0:
                 model.loss_collector.print_loss(step)
