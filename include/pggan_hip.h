@@ -640,6 +640,42 @@ int pg_record_count(const void* rec);
 int pg_replay(const void* rec);
 void pg_record_destroy(void* rec);
 
+/* ---- replay plan: cross-stream bookkeeping a recording carries and its result does not need.
+ * pg_record_optimize rewrites a recording once, on the host, over each op's kind, stream and
+ * event; it never reorders ops, and eager execution is untouched.  Two rules:
+ *   redundant waits  a wait of stream S on event E is dropped when S is already ordered, by its
+ *                    own earlier waits (followed transitively: per-stream vector clocks), behind
+ *                    the point of E's stream at which E was recorded, or when E was recorded on
+ *                    S itself.  What a stream ran before the recording (the previous replay)
+ *                    counts as work no other stream is behind yet;
+ *   dead records     only with closed != 0, the caller's promise that nothing outside this
+ *                    recording consumes an event it records -- no stream wait, and no host-side
+ *                    synchronize, query or elapsed-time call on it either (only stream waits
+ *                    inside the recording count as uses): a record of E is dropped when no
+ *                    surviving wait on E follows it before E's next record or the end.  The
+ *                    promise is refused, and the recording left exactly as it was, when the
+ *                    recording waits on an event it has not recorded earlier (stats.closed = 0).
+ * A third rule, a record right behind a launch issued as that launch's stop event
+ * (hipExtLaunchKernel), was built and measured: it gained nothing beside the dropped records
+ * and is not part of the pass (DESIGN.md "Streams").
+ * Calling it again plans the recording afresh.  `stats` may be null.
+ * pg_replay_plan_host runs the same pass on the host over n synthetic ops, three int32 each:
+ * kind (PG_OP_*), stream id, event id (any value where the kind has none), ids >= 0; flags_out
+ * [n] receives a PG_PLAN_* per op.  It needs no device. */
+#define PG_OP_LAUNCH 0
+#define PG_OP_RECORD 1
+#define PG_OP_WAIT 2
+#define PG_OP_FILL 3
+#define PG_OP_COPY 4
+#define PG_PLAN_KEEP 0
+#define PG_PLAN_DROP 1
+typedef struct pg_replay_stats {
+  int32_t ops, records, records_dropped, waits, waits_dropped;
+  int32_t closed; /* whether the closed promise was asked for and accepted */
+} pg_replay_stats;
+int pg_record_optimize(void* rec, int closed, pg_replay_stats* stats);
+int pg_replay_plan_host(const int32_t* ops, int n, int closed, int32_t* flags_out);
+
 /* ---- step plan: the kernel path of every 3x3 conv pass (forward, input
  * gradient, weight gradient) of one train_step at (stage, batch, dtype) -- the layer list of
  * pggan/nets.py:53-119 (G) and :164-239 (D) at scale_index = stage -- and the split-reduction

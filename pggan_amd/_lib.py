@@ -25,6 +25,9 @@ CONV_Y2_BITS, CONV_AUX_BITS, CONV_X_BITS, CONV_GZ_BITS = 128, 256, 512, 1024
 PACK_FWD, PACK_DGRAD = 0, 1
 LIN_BIAS, LIN_LRELU, LIN_MASK, LIN_IN_CHW, LIN_OUT_CHW, LIN_F32_IN, LIN_F32_OUT = (
     1, 2, 4, 8, 16, 32, 64)
+# the replay plan (pg_record_optimize / pg_replay_plan_host): op kinds and per-op flags
+OP_LAUNCH, OP_RECORD, OP_WAIT, OP_FILL, OP_COPY = 0, 1, 2, 3, 4
+PLAN_KEEP, PLAN_DROP = 0, 1
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpggan_hip.so")
@@ -195,6 +198,9 @@ _SIGS = {
     "pg_record_count": ([_VP], _I),
     "pg_replay": ([_VP], _I),
     "pg_record_destroy": ([_VP], None),
+    "pg_record_optimize": ([_VP, _I, _VP], _I),
+    "pg_replay_plan_host": ([ctypes.POINTER(ctypes.c_int32), _I, _I,
+                             ctypes.POINTER(ctypes.c_int32)], _I),
     "pg_stream_create": ([_I, ctypes.POINTER(ctypes.c_void_p)], _I),
     "pg_stream_destroy": ([_VP], _I),
 }
@@ -270,15 +276,48 @@ class HipEvent:
                 pass
 
 
+class ReplayStats(ctypes.Structure):
+    """pg_replay_stats (include/pggan_hip.h): what pg_record_optimize did to a recording."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("ops", "records", "records_dropped", "waits",
+                                              "waits_dropped", "closed")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+def replay_plan_host(lib, ops, closed):
+    """pg_replay_plan_host: the plan pass over synthetic (kind, stream id, event id) ops on the
+    host; a PLAN_* flag per op."""
+    n = len(ops)
+    flat = (ctypes.c_int32 * (3 * n))(*[int(v) for op in ops for v in op])
+    out = (ctypes.c_int32 * n)()
+    rc = lib.pg_replay_plan_host(flat, n, int(closed), out)
+    if rc != 0:
+        raise RuntimeError(f"replay_plan_host failed ({rc}): {lib.pg_last_error().decode()}")
+    return list(out)
+
+
 class Recording:
     """A pg_record_* recording: replay() issues the recorded launches again (pg_replay)."""
 
     def __init__(self, ops, h):
         self.lib, self.h = ops.lib, h
         self.ops = ops
+        self.plan = None
 
     def __len__(self):
         return int(self.lib.pg_record_count(self.h))
+
+    def optimize(self, closed):
+        """Plan the recording (pg_record_optimize): drop the cross-stream bookkeeping its result
+        does not need.  closed: no event it records is waited on, synchronized, queried or
+        timed outside it.  Returns and keeps
+        (self.plan) the pass's counts."""
+        st = ReplayStats()
+        self.ops._chk(self.lib.pg_record_optimize(self.h, int(bool(closed)), ctypes.byref(st)),
+                      "record_optimize")
+        self.plan = st.as_dict()
+        return self.plan
 
     def replay(self):
         self.ops._chk(self.lib.pg_replay(self.h), "replay")

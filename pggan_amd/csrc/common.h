@@ -316,12 +316,14 @@ void pg_set_error(const char* fmt, ...);
 // tuple by value -- so pg_replay can issue the same sequence again from C++ on the same streams
 // (the host enqueue of a ~380-launch training step without its Python layer, and without
 // hipGraph's re-levelling of the two streams onto other hardware queues).
+// Each recorded op carries a tag -- kind, stream, event -- that the plan pass reads
+// (pg_record_optimize, misc.hip).
 #include <functional>
 #include <tuple>
 #include <utility>
 
 bool pg_recording();
-void pg_record_push(std::function<hipError_t()> op);
+void pg_record_push(int kind, hipStream_t s, hipEvent_t ev, std::function<hipError_t()> op);
 extern "C" int pg_fill_zero(void* p, size_t bytes, void* stream);
 
 template <typename... KArgs, size_t... I>
@@ -338,7 +340,7 @@ inline void pg_launch(void (*k)(KArgs...), dim3 g, dim3 b, unsigned lds, hipStre
   std::tuple<KArgs...> t{static_cast<KArgs>(std::forward<Args>(args))...};
   (void)pg_launch_tuple(k, g, b, lds, s, t, std::index_sequence_for<KArgs...>{});
   if (pg_recording())
-    pg_record_push([=]() mutable {
+    pg_record_push(PG_OP_LAUNCH, s, nullptr, [=]() mutable {
       return pg_launch_tuple(k, g, b, lds, s, t, std::index_sequence_for<KArgs...>{});
     });
 }

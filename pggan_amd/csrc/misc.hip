@@ -6,6 +6,8 @@
 // fp32 arithmetic, one pass over each tensor.
 #include <cstdarg>
 #include <cstdio>
+#include <algorithm>
+#include <map>
 #include <vector>
 
 #include "common.h"
@@ -20,12 +22,21 @@ void pg_set_error(const char* fmt, ...) {
 }
 
 // the launch recorder (common.h: pg_launch; include/pggan_hip.h: pg_record_*)
+struct PgOp {
+  int kind;
+  hipStream_t stream;
+  hipEvent_t event;   // RECORD / WAIT
+  std::function<hipError_t()> issue;
+  int plan;           // what pg_record_optimize decided: PG_PLAN_KEEP / PG_PLAN_DROP
+};
 struct PgRecording {
-  std::vector<std::function<hipError_t()>> ops;
+  std::vector<PgOp> ops;
 };
 static thread_local PgRecording* g_rec = nullptr;
 bool pg_recording() { return g_rec != nullptr; }
-void pg_record_push(std::function<hipError_t()> op) { g_rec->ops.push_back(std::move(op)); }
+void pg_record_push(int kind, hipStream_t s, hipEvent_t ev, std::function<hipError_t()> op) {
+  g_rec->ops.push_back(PgOp{kind, s, ev, std::move(op), PG_PLAN_KEEP});
+}
 
 namespace {
 
@@ -1902,7 +1913,7 @@ int pg_event_record(void* ev, void* stream) {
   PG_CHECK_ARG(ev, "event_record: null event");
   hipEvent_t e = (hipEvent_t)ev;
   hipStream_t st = (hipStream_t)stream;
-  if (pg_recording()) pg_record_push([=]() { return hipEventRecord(e, st); });
+  if (pg_recording()) pg_record_push(PG_OP_RECORD, st, e, [=]() { return hipEventRecord(e, st); });
   return pg_hip_status(hipEventRecord(e, st), "hipEventRecord");
 }
 
@@ -1910,7 +1921,8 @@ int pg_stream_wait_event(void* stream, void* ev) {
   PG_CHECK_ARG(ev, "stream_wait_event: null event");
   hipEvent_t e = (hipEvent_t)ev;
   hipStream_t st = (hipStream_t)stream;
-  if (pg_recording()) pg_record_push([=]() { return hipStreamWaitEvent(st, e, 0); });
+  if (pg_recording())
+    pg_record_push(PG_OP_WAIT, st, e, [=]() { return hipStreamWaitEvent(st, e, 0); });
   return pg_hip_status(hipStreamWaitEvent(st, e, 0), "hipStreamWaitEvent");
 }
 
@@ -1918,7 +1930,8 @@ int pg_fill_zero(void* p, size_t bytes, void* stream) {
   PG_CHECK_ARG(p || !bytes, "fill_zero: null pointer");
   if (!bytes) return PG_OK;
   hipStream_t st = (hipStream_t)stream;
-  if (pg_recording()) pg_record_push([=]() { return hipMemsetAsync(p, 0, bytes, st); });
+  if (pg_recording())
+    pg_record_push(PG_OP_FILL, st, nullptr, [=]() { return hipMemsetAsync(p, 0, bytes, st); });
   return pg_hip_status(hipMemsetAsync(p, 0, bytes, st), "hipMemsetAsync");
 }
 
@@ -1927,7 +1940,9 @@ int pg_copy(void* dst, const void* src, size_t bytes, void* stream) {
   if (!bytes || dst == src) return PG_OK;
   hipStream_t st = (hipStream_t)stream;
   if (pg_recording())
-    pg_record_push([=]() { return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st); });
+    pg_record_push(PG_OP_COPY, st, nullptr, [=]() {
+      return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st);
+    });
   return pg_hip_status(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st), "hipMemcpyAsync");
 }
 
@@ -1953,9 +1968,124 @@ int pg_replay(const void* rec) {
   PG_CHECK_ARG(rec, "replay: null recording");
   PG_CHECK_ARG(!g_rec, "replay: not while recording");
   for (const auto& op : static_cast<const PgRecording*>(rec)->ops) {
-    const hipError_t e = op();
+    if (op.plan != PG_PLAN_KEEP) continue;
+    const hipError_t e = op.issue();
     if (e != hipSuccess) return pg_hip_status(e, "replay");
   }
+  return PG_OK;
+}
+
+// ---- the replay plan (include/pggan_hip.h: pg_record_optimize) -------------------------------
+// A pure host pass over the ops' tags.  Stream order is the only order within a stream, a wait
+// takes the latest record of its event before it in the list (the host order HIP resolves it
+// in), and a record covers every op before it on its stream.
+namespace {
+
+struct PgTag {
+  int kind;
+  intptr_t stream, event;
+};
+
+// flag[i]: a PG_PLAN_* per op
+void plan_pass(const std::vector<PgTag>& t, int closed, std::vector<int>& flag,
+               pg_replay_stats* st) {
+  const int n = (int)t.size();
+  flag.assign(n, PG_PLAN_KEEP);
+  std::map<intptr_t, int> sid, eid;
+  std::vector<int> S(n), E(n, -1);
+  for (int i = 0; i < n; ++i) {
+    S[i] = sid.emplace(t[i].stream, (int)sid.size()).first->second;
+    if (t[i].kind == PG_OP_RECORD || t[i].kind == PG_OP_WAIT)
+      E[i] = eid.emplace(t[i].event, (int)eid.size()).first->second;
+  }
+  const int ns = (int)sid.size(), ne = (int)eid.size();
+  pg_replay_stats out = {};
+  out.ops = n;
+  // a wait on an event not recorded earlier in the list has its source outside the recording:
+  // the recording is not closed, whatever the caller promises
+  bool open_wait = false;
+  {
+    std::vector<char> seen(ne, 0);
+    for (int i = 0; i < n; ++i) {
+      if (t[i].kind == PG_OP_RECORD) seen[E[i]] = 1, ++out.records;
+      if (t[i].kind == PG_OP_WAIT) open_wait |= !seen[E[i]], ++out.waits;
+    }
+  }
+  if (closed && open_wait) {
+    if (st) *st = out;
+    return;
+  }
+  out.closed = closed != 0;
+
+  // 1. redundant waits.  pos[s]: ops of stream s so far that later ops of s run behind (work and
+  // surviving waits); clk[s][u]: s is ordered behind the first clk[s][u] such ops of u.  A
+  // stream's clock moves only at its surviving waits, which pos counts, so "behind the first p
+  // ops of u" implies behind everything u itself was behind at that point.  Every stream
+  // starts at 1: whatever it ran before the recording (the previous replay) is an op too, and
+  // no stream is behind another's until it waits.
+  std::vector<int> pos(ns, 1), ev_src(ne, -1), ev_pos(ne, 0);
+  std::vector<std::vector<int>> clk(ns, std::vector<int>(ns, 0)), ev_clk(ne);
+  for (int i = 0; i < n; ++i) {
+    const int s = S[i], e = E[i];
+    if (t[i].kind == PG_OP_RECORD) {
+      ev_src[e] = s, ev_pos[e] = pos[s], ev_clk[e] = clk[s];
+      continue;
+    }
+    if (t[i].kind == PG_OP_WAIT && ev_src[e] >= 0) {
+      const int u = ev_src[e];
+      if (u == s || clk[s][u] >= ev_pos[e]) {
+        flag[i] = PG_PLAN_DROP, ++out.waits_dropped;
+        continue;
+      }
+      for (int k = 0; k < ns; ++k) clk[s][k] = std::max(clk[s][k], ev_clk[e][k]);
+      clk[s][u] = std::max(clk[s][u], ev_pos[e]);
+    }
+    ++pos[s];
+  }
+
+  // 2. dead records: no surviving wait before the event's next record or the end
+  if (closed) {
+    std::vector<char> need(ne, 0);
+    for (int i = n - 1; i >= 0; --i) {
+      if (t[i].kind == PG_OP_WAIT && flag[i] == PG_PLAN_KEEP) need[E[i]] = 1;
+      if (t[i].kind == PG_OP_RECORD) {
+        if (!need[E[i]]) flag[i] = PG_PLAN_DROP, ++out.records_dropped;
+        need[E[i]] = 0;
+      }
+    }
+  }
+
+  if (st) *st = out;
+}
+
+}  // namespace
+
+int pg_record_optimize(void* rec, int closed, pg_replay_stats* stats) {
+  PG_CHECK_ARG(rec, "record_optimize: null recording");
+  PG_CHECK_ARG(rec != g_rec, "record_optimize: not while recording");
+  auto& ops = static_cast<PgRecording*>(rec)->ops;
+  std::vector<PgTag> tags;
+  tags.reserve(ops.size());
+  for (const auto& op : ops) tags.push_back(PgTag{op.kind, (intptr_t)op.stream, (intptr_t)op.event});
+  std::vector<int> flag;
+  plan_pass(tags, closed, flag, stats);
+  for (size_t i = 0; i < ops.size(); ++i) ops[i].plan = flag[i];
+  return PG_OK;
+}
+
+int pg_replay_plan_host(const int32_t* ops, int n, int closed, int32_t* flags_out) {
+  PG_CHECK_ARG(n >= 0 && (n == 0 || (ops && flags_out)), "replay_plan_host: null argument");
+  std::vector<PgTag> tags(n);
+  for (int i = 0; i < n; ++i) {
+    const int32_t kind = ops[3 * i], s = ops[3 * i + 1], e = ops[3 * i + 2];
+    const bool ev = kind == PG_OP_RECORD || kind == PG_OP_WAIT;
+    PG_CHECK_ARG(kind >= PG_OP_LAUNCH && kind <= PG_OP_COPY && s >= 0 && (!ev || e >= 0),
+                 "replay_plan_host: op %d: bad kind or id", i);
+    tags[i] = PgTag{kind, s, ev ? e : 0};
+  }
+  std::vector<int> flag;
+  plan_pass(tags, closed, flag, nullptr);
+  for (int i = 0; i < n; ++i) flags_out[i] = flag[i];
   return PG_OK;
 }
 

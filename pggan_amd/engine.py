@@ -208,6 +208,10 @@ ENGINE_DEFAULTS = dict(
     tail_b=True,           # ... with tail_main: the top level's conv-b weight gradient too
     tail_levels=1,         # ... and both weight gradients of this many top levels
     fuse_rgbo=False,       # the toRGB output in the epilogue of the top conv b: measured -1 % (opt-in)
+    # the C++ replay of a recorded step without the cross-stream bookkeeping its result does not
+    # need (pg_record_optimize, DESIGN.md "Streams"); 0: re-issue the recording as recorded;
+    # 2: never promise a closed recording (wait pruning only: what DP segments get)
+    replay_plan=1,
 )
 
 

@@ -31,6 +31,7 @@ from __future__ import annotations
 
 import math
 import os
+import sys
 
 import numpy as np
 import torch
@@ -104,6 +105,19 @@ class _Segments:
 
     def __len__(self):
         return sum(len(x) for x in self.segs if hasattr(x, "replay"))
+
+    def optimize(self, closed):
+        """Plan every launch recording (`_lib.Recording.optimize`); the counts, summed.  A
+        recording is closed -- nothing outside it waits on, synchronizes, queries or times an
+        event it records -- only when the caller says so and it is the whole step: with host
+        actions between segments an event may be recorded in one segment and waited on in the
+        next."""
+        recs = [x for x in self.segs if hasattr(x, "optimize")]
+        total = {}
+        for x in recs:
+            for k, v in x.optimize(closed and len(self.segs) == 1).items():
+                total[k] = total.get(k, 0) + v
+        return total
 
 
 class ProgressiveGAN:
@@ -553,6 +567,14 @@ class ProgressiveGAN:
                         self._exchange.record_hook = None
                     if ok:
                         gs["rec"] = _Segments(segs)
+                        plan = int(getattr(eng, "replay_plan", 0))
+                        if plan:
+                            # closed: one process, and the step left no side-stream event for
+                            # a later step to join on
+                            gs["plan"] = gs["rec"].optimize(
+                                plan == 1 and self._exchange is None and not eng._side_ev)
+                            if os.environ.get("PG_REPLAY_LOG"):
+                                print(f"[replay plan] {gs['plan']}", file=sys.stderr, flush=True)
                         # the engine's host state after the step (a deferred generator update
                         # under DP, the merged-forward flags): a replay runs no Python, so it
                         # restores what the recorded step left behind.  The Adam steps the
